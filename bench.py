@@ -22,8 +22,15 @@ ranks' rays / the slowest rank's time; the efficiency against the N = 1 frame is
 spp``) and, with ``--shard sample``, every rank tracing its own full-frame sample with no collective.
 
 N = 1: the whole frame as one launch per bounce with 3 frames in flight, every frame slot its own jittered
-sample; after the timed steps every slot's records (both bounces, both _PrimaryTriangleInfo forms) are
-compared with the oracle traced from the same pre-state (``oracle_check``, ``oracle_identical``).
+sample; under ``--full``, after the timed steps every slot's records (both bounces, both _PrimaryTriangleInfo
+forms) are compared with the oracle traced from the same pre-state (``oracle_check``, ``oracle_identical``).
+
+A plain run (no ``--full``) does what the headline needs and nothing else: setup, W warm-up steps, K timed steps
+(``ms_per_step`` = the timed region / K), ``--dump-outputs DIR`` if given (the last timed step's records as .npy
+files, dump_outputs below) and the JSON line. Every other leg -- the roofline fraction's single-stream launches,
+the CPU baseline, the oracle check, the other layouts and BASELINE configs -- is measured under ``--full`` only,
+and its field of the JSON line is null without it. (A plain run still issues the single-stream launches before
+the timed region and reports nothing of them: they settle the clocks, see main.)
 
 Streams: torch and the engine share ONE stream (a torch.cuda.Stream made current before any
 allocation and passed to tt_ctx_create), so every torch copy / collective and every engine launch
@@ -921,6 +928,69 @@ def oracle_records_check(scene, layout, pre, post, colors, far, W, H):
             "seconds": round(time.perf_counter() - t0, 2)}
 
 
+DUMP_ROWS = 200_000  # rows sampled per dumped array: 2 x 5 + 2 x 4 float64 columns, ~29 MB in all
+
+
+def dump_outputs(torch, layout, dirname, seed, rank, world):
+    """--dump-outputs: what the last timed step left in its frame slot's buffers, i.e. what the caller of that
+    step's launches receives -- the hit records (RayData.hits) of its primary and bounce-1 rays and the two
+    _PrimaryTriangleInfo forms -- as float64 arrays DIR/<name>.npy (<name>_rank<r> at N > 1). Every array is the
+    same seeded sample of at most DUMP_ROWS rows in buffer order (the row numbers are a function of --seed and the
+    row count alone), so two builds run with the same arguments write comparable files.
+      primary_hits, bounce_hits  (rows, 5): mesh_id, triangle_id (-1: miss), t, u, v (the 16-bit uv unpacked)
+      primary_info               (rows, 4): bounce 0's texels: mesh_id, triangle id within the mesh, u, v
+      bounce_info                (rows, 4): the bounce-1 form's texels, the four 32-bit words as integers (a texel
+                                            the step does not write -- a bounce ray that missed -- keeps the buffer's
+                                            fill: zero, or the poison byte of --full's oracle check)
+      counts                     (2,): the step's primary and bounce-1 ray counts"""
+    os.makedirs(dirname, exist_ok=True)
+    torch.cuda.synchronize(layout.dev)
+    f, r = layout.last_slot(), layout.cycle_of(layout.k - 1)
+    row = layout.slots[f]
+    WHs = layout.W * layout.Hs
+    rng = np.random.default_rng(seed)
+
+    def sample(t, n, width, most):
+        """`most` of the first n rows of the device byte buffer t (rows of `width` bytes), as host uint32 words."""
+        if n <= 0:
+            return np.zeros((0, width // 4), np.uint32)
+        idx = np.sort(rng.choice(n, size=min(n, most), replace=False))
+        got = t.view(-1, width)[:n][torch.from_numpy(idx).to(t.device)].cpu().numpy()
+        return np.ascontiguousarray(got).view(np.uint32).reshape(len(idx), width // 4)
+
+    def hits(words):
+        h = np.ascontiguousarray(words[:, 8:12])
+        out = np.empty((len(h), 5), np.float64)
+        out[:, 0:2] = h.view(np.int32)[:, 0:2]
+        out[:, 2] = h.view(np.float32)[:, 2]
+        out[:, 3] = (h[:, 3] & 0xFFFF) / 65535.0
+        out[:, 4] = (h[:, 3] >> 16) / 65535.0
+        return out
+
+    per_part = max(1, DUMP_ROWS // len(row))
+    prim = np.concatenate([sample(p.rays_r[r], p.n, 48, per_part) for p in row])
+    bnc = np.concatenate([sample(p.rays_r[r][WHs * 48:], p.nb_r[r], 48, per_part) for p in row]) \
+        if layout.bounce else np.zeros((0, 12), np.uint32)
+    arrays = {"primary_hits": hits(prim), "bounce_hits": hits(bnc),
+              "counts": np.array([sum(p.n for p in row), sum(p.nb_r[r] for p in row)], np.float64)}
+    if layout.info0[f] is not None:
+        i0 = sample(layout.info0[f], WHs, 16, DUMP_ROWS)
+        a = np.empty((len(i0), 4), np.float64)
+        a[:, 0:2] = i0.view(np.int32)[:, 0:2]
+        a[:, 2:4] = i0.view(np.float32)[:, 2:4]
+        arrays["primary_info"] = a
+    if layout.info1[f] is not None:
+        arrays["bounce_info"] = sample(layout.info1[f], WHs, 16, DUMP_ROWS).astype(np.float64)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    total = 0
+    for name, a in arrays.items():
+        path = os.path.join(dirname, name + suffix + ".npy")
+        np.save(path, a)
+        total += os.path.getsize(path)
+    assert total <= 64 << 20, total
+    return {"dir": dirname, "slot": f, "arrays": {k + suffix: list(a.shape) for k, a in arrays.items()}, "bytes": total}
+
+
 def cpu_share():
     """(hardware threads, CPUs this process may run on, cgroup CPU quota or None)."""
     hw = os.cpu_count() or 1
@@ -1064,6 +1134,17 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--tris", type=int, default=262267)
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x53504F4E)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: the oracle check of the timed records, the CPU "
+                         "baseline, the single-stream / steady-state / interactive / unjittered / shadow / producer / "
+                         "group legs, the parity of the last frame against one launch, the other BASELINE configs "
+                         "(--aux) and, at N > 1, the other multi-GPU layouts. Without it a run sets up, warms up, times "
+                         "the steps, writes --dump-outputs and prints the result line (those legs' fields null); the "
+                         "--no-* options below trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its frame slot's hit records "
+                         "of both bounces and both _PrimaryTriangleInfo forms, a fixed seeded sample of rows, float64) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline budget (rank 0, N=1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-oracle-check", action="store_true",
@@ -1147,6 +1228,10 @@ def main():
                     help="other BASELINE configs to measure after the metric at N=1 (comma list of c3,c4,dyn,refit,c5;"
                          " '' = none)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline only; every other leg belongs to --full
+        args.no_cpu_baseline = args.no_oracle_check = args.no_shadow = args.no_single = args.no_recur = True
+        args.no_group = args.no_c5_tiles = args.no_spp_aux = args.no_strong = True
+        args.steady_steps, args.aux = 0, ""
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None:
@@ -1344,11 +1429,14 @@ def main():
         onb = eng.enqueue_bounce(one, WH, 0, far, W, H, frames=frames, max_bounce=1, device=True)
         o_bnc = eng.trace(one, onb, 1, far, W, H, info=info, colors=colors_t, device=True, stats=True)
         frame_rays, frame_nb = one, onb
-        if not args.no_single:
+        # (a plain run issues the same launches and reports nothing of them: they are the sustained work that
+        # settles the clocks before the timed region, so `value` means what it does under --full)
+        if not args.no_single or not args.full:
             launches = [lambda: eng.trace(one, WH, 0, far, W, H, info=info, device=True, asynchronous=True),
                         lambda: eng.trace(one, onb, 1, far, W, H, info=info, colors=colors_t, device=True,
                                           asynchronous=True)]
             oms = timed_launches(eng, launches, args.warmup, args.steps)
+        if not args.no_single:
             o_avg = float(oms.mean())
             o_ach = ((alg_bytes(o_prim, 0, WH) + alg_bytes(o_bnc, 1, onb)) / 2.0) / (o_avg * 1e-3) / 1e9
             single = {"achieved": round(o_ach, 1), "frac": round(o_ach / HBM_PEAK_GBS, 4),
@@ -1359,7 +1447,7 @@ def main():
 
     # secondary N > 1 layout: every rank traces its own full-frame jittered sample (weak scaling)
     sample_sharded = None
-    if tiles:
+    if tiles and args.full:
         srays = torch.zeros(2 * WH * 48, dtype=torch.uint8, device=dev)
         eng.generate(srays, c2w, ip, W, H, 0.3, far, jitter=1, frames=rank, max_bounce=1, device=True)
         eng.trace(srays, WH, 0, far, W, H, device=True)
@@ -1421,6 +1509,10 @@ def main():
     # the frame, profiles/r05/events/); the launch times below come from K more steps right after it
     layout.time_none = world > 1
     elapsed = timed(layout)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(torch, layout, args.dump_outputs, args.seed, rank, world)
+        log(f"rank {rank}: wrote {dumped['bytes']} bytes of the last timed step's outputs to {args.dump_outputs}")
     if world > 1:
         layout.time_none = False
         layout.timing_reset()
@@ -1482,7 +1574,7 @@ def main():
     gather_parity = None
     if G is not None:
         sizes, gather_list = layout.last_gathered()  # the last step's gather (steady-state steps included)
-    if (split or F > 1) and rank == 0:
+    if (split or F > 1) and rank == 0 and args.full:
         last = layout.last_slot()  # the last frame's slot; its samples are layout.last_sample(k)
         r_last = layout.cycle_of(layout.k - 1)
         if spp:
@@ -1570,7 +1662,7 @@ def main():
     # camera: each frame's Generate may take a new pose, RayGenKernels.compute:40-57) x N1_SLOTS frames in flight.
     # The headline's B frames per launch need the next B cameras up front, i.e. a still view accumulating samples.
     interactive = None
-    if world == 1 and layout.B > 1:
+    if world == 1 and layout.B > 1 and args.full:
         lay_i = layout_of([[(frames, np.arange(WH, dtype=np.int64))]], N1_SLOTS)
         el_i = timed(lay_i)
         lay_i.launch_ms()
@@ -1672,7 +1764,7 @@ def main():
     # Generate (1080p primary rays) and the diffuse-bounce enqueue with wave-ballot compaction (counter
     # reset + kernel), on a scratch copy of the traced rays restored before every call; engine timing ring.
     producers = None
-    if world == 1:  # on the full-frame buffer in the kernel's own order (the parts hold compacted tiles)
+    if world == 1 and args.full:  # on the full-frame buffer in the kernel's own order (the parts hold compacted tiles)
         scratch = frame_rays.clone()
         eng.timing_reset()
         for k in range(args.steps):
@@ -1835,6 +1927,8 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 4),
+        "full": bool(args.full),
+        "dump_outputs": dumped,
         "higher_is_better": True,
         # the job's scaling mode, the same at every N: spp / sample keep per-GPU work fixed as N grows
         "scaling": "strong" if args.shard == "tiles" else "weak",

@@ -83,7 +83,7 @@ def test_bench_self_launch_two_ranks_gloo_on_one_gpu():
     headline's strong-scaling tile layout (one 1080p frame's tiles over the ranks, one gather per step); rank 0's JSON line reports 2 GPUs and a gathered frame identical to one GPU
     tracing the whole frame, and the weak-scaling spp layout beside it (a 2-sample frame, same gather)
     identical too."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, BENCH, "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
                         "--no-shadow", "--no-c5-tiles", "--steady-steps", "0"],
                        env=_env(TT_BENCH_DIST_BACKEND="gloo"), capture_output=True, text=True, timeout=170)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -4,7 +4,7 @@
 # Stages run in order, each under its own time limit, outputs in gpurun_out/TAG/; the job stops at
 # the first failing stage (no GPU step runs after a failure). Stages:
 #   tests      pytest -m gpu (the parity suite)
-#   bench      the driver's command: python bench.py --gpus 1 --steps 20 --warmup 5
+#   bench      every leg of the bench: python bench.py --full --gpus 1 --steps 20 --warmup 5
 #   group      the multi-GPU group (tt_group_*), batched-frame oracle and lifecycle GPU tests
 #   groupbench the bench headline + aux_group_tiles (the library's group path) + interactive, no other aux legs
 #   smoke      __graft_entry__.smoke() (the driver runs it before the bench)
@@ -62,27 +62,27 @@ for stage in "$@"; do
     case $stage in
     tests) run tests 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread || exit $? ;;
     blocks) for i in $(seq ${REPS:-1}); do for b in ${BLOCKS:-20 16}; do  # persistent grid blocks per CU (env knob)
-                run "blocks_${b}_$i" 300 env TT_BLOCKS_PER_CU=$b python -u bench.py --steps 20 --warmup 5 --aux "" \
+                run "blocks_${b}_$i" 300 env TT_BLOCKS_PER_CU=$b python -u bench.py --full --steps 20 --warmup 5 --aux "" \
                     --no-cpu-baseline --no-recur --no-shadow || exit $?
             done; done ;;
     group) run group 900 env TT_TEST_ROCPROF=1 python -u -m pytest -x -v --timeout 400 --timeout-method thread \
                tests/test_gpu_group.py tests/test_gpu_batch_oracle.py tests/test_gpu_lifecycle.py -m gpu || exit $? ;;
-    groupbench) run groupbench 400 python -u bench.py --steps 20 --warmup 5 --aux "" --no-cpu-baseline --no-recur \
+    groupbench) run groupbench 400 python -u bench.py --full --steps 20 --warmup 5 --aux "" --no-cpu-baseline --no-recur \
                     --no-shadow --no-single ${GB_ARGS:-} || exit $? ;;
     smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-    bench) run bench 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 || exit $? ;;
-    quick) run quick 300 python -u bench.py --steps 20 --warmup 5 --aux "" --cpu-seconds 2 || exit $? ;;
+    bench) run bench 600 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 || exit $? ;;
+    quick) run quick 300 python -u bench.py --full --steps 20 --warmup 5 --aux "" --cpu-seconds 2 || exit $? ;;
     dyn) for b in ${BLOCKS:-0}; do  # the headline + the C4 dynamic frame (one launch and frame slots) per grid cap
-             run "dyn_b$b" 400 env TT_BLOCKS_PER_CU=$b python -u bench.py --steps 20 --warmup 5 --aux dyn \
+             run "dyn_b$b" 400 env TT_BLOCKS_PER_CU=$b python -u bench.py --full --steps 20 --warmup 5 --aux dyn \
                  --no-cpu-baseline --no-recur --no-shadow ${DYN_ARGS:-} || exit $?
          done ;;
     dyndiag) for d in ${DIAGS:-none noupdate nogen noupdate,nogen}; do  # the C4 dynamic frame without one per-frame call
-                 run "dyndiag_$d" 400 python -u bench.py --steps 20 --warmup 5 --aux dyn --no-cpu-baseline --no-recur \
+                 run "dyndiag_$d" 400 python -u bench.py --full --steps 20 --warmup 5 --aux dyn --no-cpu-baseline --no-recur \
                      --no-shadow --no-oracle-check --dyn-diag "$d" ${DYN_ARGS:-} || exit $?
              done ;;
-    slots2) run slots2 300 python -u bench.py --steps 20 --warmup 5 --aux "" --no-cpu-baseline --slots 2 || exit $? ;;
+    slots2) run slots2 300 python -u bench.py --full --steps 20 --warmup 5 --aux "" --no-cpu-baseline --slots 2 || exit $? ;;
     layouts) for i in $(seq ${REPS:-2}); do for l in ${LAYOUTS:-2x1 2x2 1x3}; do  # N = 1 headline per parts x slots
-                 run "n1_${l}_$i" 300 python -u bench.py --steps 20 --warmup 5 --aux "" --no-cpu-baseline --no-recur \
+                 run "n1_${l}_$i" 300 python -u bench.py --full --steps 20 --warmup 5 --aux "" --no-cpu-baseline --no-recur \
                      --no-shadow --parts ${l%x*} --slots ${l#*x} || exit $?
              done; done ;;
     testlib) lib=$PWD/truetrace-unity-pathtracer_amd/lib/variants/libtruetrace_hip_${LIB:?set LIB=variant name}.so
@@ -130,12 +130,12 @@ for stage in "$@"; do
                        --primary-only ${ORDER_ARGS:-} || exit $?
                done
            done ;;
-    gloo2) run gloo2 600 env TT_BENCH_DIST_BACKEND=gloo python -u bench.py --gpus 2 --steps 4 --warmup 1 \
+    gloo2) run gloo2 600 env TT_BENCH_DIST_BACKEND=gloo python -u bench.py --full --gpus 2 --steps 4 --warmup 1 \
                --no-cpu-baseline --no-shadow --steady-steps 0 || exit $? ;;
     groupscale) run groupscale 600 python -u tools/group_scale.py ${GS_FRAMES:-200} || exit $? ;;
-    rccl1) run rccl1 600 env TT_BENCH_RCCL_WORLD1=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29611 python -u bench.py --steps 4 --warmup 1 --no-cpu-baseline \
+    rccl1) run rccl1 600 env TT_BENCH_RCCL_WORLD1=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29611 python -u bench.py --full --steps 4 --warmup 1 --no-cpu-baseline \
                --no-shadow --steady-steps 0 --aux "" || exit $? ;;
-    gloo4) run gloo4 600 env TT_BENCH_DIST_BACKEND=gloo python -u bench.py --gpus 4 --steps 4 --warmup 1 \
+    gloo4) run gloo4 600 env TT_BENCH_DIST_BACKEND=gloo python -u bench.py --full --gpus 4 --steps 4 --warmup 1 \
                --no-cpu-baseline --no-shadow --steady-steps 0 || exit $? ;;
     sweep) n=${SWEEP_N:-300}; s0=${SWEEP_SEED:-40000}  # plain; trace variants + adaptive order; + degenerate directions
            run sweep_plain 900 python -u tools/parity_sweep.py $n $s0 || exit $?
@@ -156,7 +156,7 @@ for stage in "$@"; do
     ab) for i in $(seq ${REPS:-1}); do for v in ${AB_LIBS:-product}; do  # the bench headline per library variant, in turn
             lib=truetrace-unity-pathtracer_amd/lib/variants/libtruetrace_hip_$v.so
             [ "$v" = product ] && lib=truetrace-unity-pathtracer_amd/lib/libtruetrace_hip.so
-            run "ab_${v}_$i" 300 env TT_HIP_LIB=$lib python -u bench.py --steps 20 --warmup 5 --aux "" --no-cpu-baseline \
+            run "ab_${v}_$i" 300 env TT_HIP_LIB=$lib python -u bench.py --full --steps 20 --warmup 5 --aux "" --no-cpu-baseline \
                 --no-recur --no-shadow ${AB_ARGS:-} || exit $?
         done; done ;;
     abcfg) for v in ${AB_LIBS:-product}; do  # one-launch C4 / C5 per variant (tools/run_variants.py)
