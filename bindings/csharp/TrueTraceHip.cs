@@ -197,6 +197,10 @@ namespace TrueTrace.Hip
         [DllImport(Lib)] public static extern TTStatus tt_timing_reset(IntPtr ctx);
         [DllImport(Lib)] public static extern unsafe TTStatus tt_timing_read(IntPtr ctx, float* ms, uint max, out uint n);
         [DllImport(Lib)] public static extern unsafe TTStatus tt_trace_diagnostics(IntPtr ctx, ulong* out8);
+        // kernel form of the last trace launch: 0 none, 1 generic, 2 leaf-TLAS (TT_TRACE_FORM_*)
+        [DllImport(Lib)] public static extern TTStatus tt_trace_last_form(IntPtr ctx, out uint form);
+        // what a TLAS's node 0 (80 bytes) is: 0 generic, 1 one leaf, 2 one leaf of one instance (TT_ROOT_*)
+        [DllImport(Lib)] public static extern TTStatus tt_tlas_root_form(IntPtr node0, out uint form);
         [DllImport(Lib)] public static extern TTStatus tt_selftest_rcp(IntPtr ctx, out ulong mismatches);
         // multi-GPU tile-sharded frames (one process driving n devices, or one rank per process)
         [DllImport(Lib)] public static extern unsafe TTStatus tt_group_create(int* devices, uint n, ref TTGroupConfig cfg,

@@ -525,6 +525,25 @@ tt_status tt_ctx_set_frame_pixels(tt_ctx* ctx, uint32_t frame_pixels);
  * same node as the wave's first node-phase lane, wave-uniform node phases. */
 tt_status tt_trace_diagnostics(const tt_ctx* ctx, uint64_t* out8);
 
+/* Which form of the closest-hit kernel the context's last trace launch (tt_trace_closest, _hits, _indirect)
+ * took. The leaf-TLAS form serves scenes whose TLAS root is one leaf holding one instance (one imported
+ * mesh): launches without TT_TRACE_STATS, the material check or TT_TRACE_ADAPTIVE_ORDER, while the host knows
+ * node 0 (not after a device tt_tlas_refit until the next node update). Results are bit-identical in both
+ * forms; the environment variable TT_LEAF_KERNEL=0 (read once per process) forces the generic form. */
+enum {
+    TT_TRACE_FORM_NONE = 0,    /* no trace launch yet */
+    TT_TRACE_FORM_GENERIC = 1, /* the two-level kernel */
+    TT_TRACE_FORM_LEAF = 2     /* the leaf-TLAS kernel */
+};
+tt_status tt_trace_last_form(const tt_ctx* ctx, uint32_t* form);
+/* The selection predicate on its own (host only, no device needed): what node 0 of a TLAS is. */
+enum {
+    TT_ROOT_GENERIC = 0,     /* an internal child, or more than one child */
+    TT_ROOT_ONE_LEAF = 1,    /* one child, a leaf of 2-3 instances: the generic kernel with its root shortcut */
+    TT_ROOT_ONE_INSTANCE = 2 /* one child, a leaf of one instance: qualifies for the leaf-TLAS kernel */
+};
+tt_status tt_tlas_root_form(const tt_cwbvh_node* node0, uint32_t* form);
+
 /* Self-test of the fast reciprocal the kernels use for rcp() (numerics contract: correctly
  * rounded 1.0f/x): evaluates it and the full IEEE division for all 2^32 fp32 bit patterns on the
  * context's device and returns the number of inputs whose results differ (bitwise, NaN == NaN) in

@@ -18,7 +18,7 @@ vals = collections.defaultdict(lambda: collections.defaultdict(list))
 for f in glob.glob(f"{src}/**/*counter_collection.csv", recursive=True):
     per = collections.defaultdict(lambda: collections.defaultdict(float))
     for r in csv.DictReader(open(f)):
-        if "tt_trace_kernel" not in r["Kernel_Name"]:
+        if "tt_trace_kernel" not in r["Kernel_Name"] and "tt_trace_leaf_kernel" not in r["Kernel_Name"]:
             continue
         per[(r["Kernel_Name"].split("(")[0], r["Dispatch_Id"])][r["Counter_Name"]] += float(r["Counter_Value"])
     for (k, _), cs in per.items():
@@ -35,9 +35,12 @@ for k, cs in vals.items():
 # bench.py launches the primary and the bounce instantiation equally often
 # (the timed launches are the non-STATS closest-hit instantiations; STATS launches run once in setup)
 # (<false, false, 1>: primary with _PrimaryTriangleInfo, <false, false, 2>: bounce-1 with the Data.w-gated
-# info; the parity check's full-frame <false, false, 0> launch and the aux configs are not the metric's)
+# info; the parity check's full-frame <false, false, 0> launch and the aux configs are not the metric's).
+# The bench scene has a one-instance TLAS, so its timed launches take the leaf-TLAS kernels
+# (tt_trace_leaf_kernel<false, INFO>) unless TT_LEAF_KERNEL=0 forces the generic ones.
 timed = {k: v for k, v in per_kernel.items()
-         if k.replace(" ", "") in ("voidtt_trace_kernel<false,false,1>", "voidtt_trace_kernel<false,false,2>")}
+         if k.replace(" ", "") in ("voidtt_trace_kernel<false,false,1>", "voidtt_trace_kernel<false,false,2>",
+                                   "voidtt_trace_leaf_kernel<false,1>", "voidtt_trace_leaf_kernel<false,2>")}
 res = {"file": out.split("/")[-1], "source": src,
        "correction": "read = 2 x FETCH_SIZE (gfx950), write = WRITE_SIZE; includes Infinity-Cache hits",
        "per_kernel": per_kernel, "timed_kernels": sorted(timed),

@@ -10,8 +10,8 @@ tools/pmc_units.sh passes (one rocprofv3 --pmc run per counter group on
                                for the instruction stream the kernel runs)
 
 Rays per dispatch come from the bench JSON line each pass printed (config.primary_rays /
-config.bounce_rays): tt_trace_kernel<..., 1> is the primary launch (INFO = 1), <..., 2> the
-bounce-1 launch. Writes the JSON bench.py reads for `roofline` (profiles/units_latest.json).
+config.bounce_rays): tt_trace_kernel<..., 1> (tt_trace_leaf_kernel<false, 1> for a one-instance scene, which
+the bench's is) is the primary launch (INFO = 1), <..., 2> the bounce-1 launch. Writes the JSON bench.py reads for `roofline` (profiles/units_latest.json).
 Usage: python tools/pmc_units_summary.py gpurun_out/pmcu profiles/units_latest.json"""
 import collections
 import csv
@@ -41,7 +41,9 @@ def main():
     for f in sorted(glob.glob(f"{root}/*/*_counter_collection.csv")):
         per = collections.defaultdict(lambda: collections.defaultdict(float))
         for r in csv.DictReader(open(f)):
-            if "tt_trace_kernel<false" not in r["Kernel_Name"] and "tt_trace_kernel_ord<" not in r["Kernel_Name"]:
+            # (the non-stats generic kernels, the adaptive-order kernels, the direct leaf-TLAS kernels)
+            if not any(s in r["Kernel_Name"] for s in ("tt_trace_kernel<false", "tt_trace_kernel_ord<",
+                                                       "tt_trace_leaf_kernel<false")):
                 continue
             per[(r["Kernel_Name"].split("(")[0], r["Dispatch_Id"])][r["Counter_Name"]] += float(r["Counter_Value"])
         # an adaptive-order kernel's first dispatch has no order yet (it only records costs): skip it

@@ -25,9 +25,10 @@
 #define TT_TLAS_SLOTS 8u
 #endif
 
-hipError_t tt_launch_trace(const TraceArgs& a, bool stats, bool matcheck, int info, uint32_t grid, hipStream_t st);
+hipError_t tt_launch_trace(const TraceArgs& a, bool stats, bool matcheck, int info, bool leaf, uint32_t grid,
+                           hipStream_t st);
 uint32_t tt_trace_chunk_rays();
-hipError_t tt_trace_occupancy_table(int* out18);
+hipError_t tt_trace_occupancy_table(int* out24);
 hipError_t tt_launch_shadow(const ShadowArgs* a, uint32_t grid, hipStream_t st, int stats, int matcheck);
 hipError_t tt_launch_shadow_accumulate(const ShadowArgs* a, const float4* vis, hipStream_t st);
 void tt_shadow_occupancy_table(int* out4);
@@ -117,7 +118,9 @@ struct tt_ctx {
     int num_cus = 0;
     int blocks_per_cu = 0;
     uint32_t grid = 0;
-    uint32_t grid_of[18] = {};  // resident persistent grid per kernel instantiation (12..17: adaptive order)
+    uint32_t grid_of[24] = {};  // resident persistent grid per kernel instantiation (12..17: adaptive order,
+                                // 18..23: the leaf-TLAS kernels, direct and indirect)
+    uint32_t last_form = TT_TRACE_FORM_NONE;  // the kernel form of the last closest-hit launch (tt_trace_last_form)
     uint32_t shadow_grid_of[4] = {};  // the same for the any-hit kernel (stats * 2 + matcheck)
     TraceControl* ctl = nullptr;  // two control blocks: a trace launch uses one and zeroes the other
     uint32_t* sticky = nullptr;   // stack overflows of every launch since the last tt_async_overflows
@@ -924,7 +927,7 @@ tt_status tt_ctx_create(const tt_config* cfg, tt_ctx** out) {
         return TT_ERR_HIP;
     }
     c->num_cus = prop.multiProcessorCount;
-    int occ[18];
+    int occ[24];
     (void)tt_trace_occupancy_table(occ);
     // Residency check beyond the occupancy API: measured on MI355X, five 32-KiB-LDS blocks were
     // not co-resident (the fifth started only when another exited), consistent with the LDS being
@@ -936,7 +939,7 @@ tt_status tt_ctx_create(const tt_config* cfg, tt_ctx** out) {
     // at most 32 waves per CU (8 blocks of 4 waves at the default 256-thread block)
     const int wpb = (int)std::max(1u, tt_trace_block_size() / 64u);
     const int block_cap = std::max(1, 32 / wpb);
-    for (int k = 0; k < 18; k++) {
+    for (int k = 0; k < 24; k++) {
         int b = std::max(1, std::min(std::min(occ[k], lds_cap), block_cap));
         if (knob > 0 && knob < b) b = knob;
         c->grid_of[k] = (uint32_t)(c->num_cus * b);
@@ -951,7 +954,7 @@ tt_status tt_ctx_create(const tt_config* cfg, tt_ctx** out) {
     c->blocks_per_cu = (int)(c->grid_of[1] / c->num_cus);
     c->grid = c->grid_of[1];
     uint32_t max_grid = 0;
-    for (int k = 0; k < 18; k++) max_grid = std::max(max_grid, c->grid_of[k]);
+    for (int k = 0; k < 24; k++) max_grid = std::max(max_grid, c->grid_of[k]);  // (the spill area: the largest grid)
     for (int k = 0; k < 4; k++) max_grid = std::max(max_grid, c->shadow_grid_of[k]);
     c->spill_threads = max_grid * tt_trace_block_size();
     // two control blocks + the sticky overflow counter behind them
@@ -1084,6 +1087,19 @@ tt_status tt_timing_read(tt_ctx* c, float* ms, uint32_t max, uint32_t* n) {
 tt_status tt_trace_diagnostics(const tt_ctx* c, uint64_t* out8) {
     if (!c || !out8) return TT_ERR_INVALID_ARG;
     for (int k = 0; k < 8; k++) out8[k] = c->last_diag[k];
+    return TT_OK;
+}
+
+tt_status tt_trace_last_form(const tt_ctx* c, uint32_t* form) {
+    if (!c || !form) return TT_ERR_INVALID_ARG;
+    *form = c->last_form;
+    return TT_OK;
+}
+
+tt_status tt_tlas_root_form(const tt_cwbvh_node* node0, uint32_t* form) {
+    if (!node0 || !form) return TT_ERR_INVALID_ARG;
+    const RootLeaf r = root_leaf_of(reinterpret_cast<const uint32_t*>(node0));
+    *form = root_one_instance(r) ? TT_ROOT_ONE_INSTANCE : r.ok ? TT_ROOT_ONE_LEAF : TT_ROOT_GENERIC;
     return TT_OK;
 }
 
@@ -2008,8 +2024,17 @@ static tt_status trace_closest_call(tt_ctx* c, const tt_trace_params* p, const u
     const uint32_t waves_needed = (chunks_needed + chunks_per_wave - 1u) / chunks_per_wave;
     const uint32_t wpb = std::max(1u, tt_trace_block_size() / 64u);  // waves per block
     const uint32_t blocks_needed = (waves_needed + wpb - 1u) / wpb;
-    const uint32_t grid = std::max(
-        1u, std::min(c->grid_of[(adaptive ? 12 : want_stats ? 6 : 0) + (matcheck ? 3 : 0) + info_mode], blocks_needed));
+    // The leaf-TLAS kernels (tt_trace.hip): node 0, known to the host, is one leaf holding exactly one instance
+    // (a device TLAS refit clears root_known, so a.root.ok is 0 until the next node update), and the launch wants
+    // no stats, no material check and no adaptive order. TT_LEAF_KERNEL=0 forces the generic kernels (A/B, tests).
+    static const bool leaf_enabled = [] {
+        const char* e = std::getenv("TT_LEAF_KERNEL");
+        return !(e && std::atoi(e) == 0);
+    }();
+    const bool leaf = leaf_enabled && root_one_instance(a.root) && !want_stats && !matcheck && !adaptive;
+    const uint32_t grid_index = leaf ? 18u + (n_dev ? 3u : 0u) + (uint32_t)info_mode
+                                     : (adaptive ? 12u : want_stats ? 6u : 0u) + (matcheck ? 3u : 0u) + (uint32_t)info_mode;
+    const uint32_t grid = std::max(1u, std::min(c->grid_of[grid_index], blocks_needed));
     // TT_TRACE_ADAPTIVE_ORDER: this launch fills cost[cur ^ 1] (per 64-ray chunk); with the previous
     // launch's costs in cost[cur] the order kernel (inside the timed entry) sorts this launch's chunks
     tt_ctx::OrderSlot* os = nullptr;
@@ -2064,7 +2089,8 @@ static tt_status trace_closest_call(tt_ctx* c, const tt_trace_params* p, const u
         TT_HIP(c, tt_launch_order(o, c->stream));
         a.order = os->order.p;
     }
-    TT_HIP(c, tt_launch_trace(a, want_stats, matcheck, info_mode, grid, c->stream));
+    TT_HIP(c, tt_launch_trace(a, want_stats, matcheck, info_mode, leaf, grid, c->stream));
+    c->last_form = leaf ? TT_TRACE_FORM_LEAF : TT_TRACE_FORM_GENERIC;
     note_stream_launch(c->stream);
     if (os) {
         os->cur ^= 1u;

@@ -16,21 +16,36 @@
 // Numerics follow include/truetrace_hip.h (compiled with -ffp-contract=off).
 #include "tt_wide.h"
 
+// TT_REFILL_MIN of the leaf-TLAS kernels (trace_body<LEAF>), whose ray start is cheaper: a knob of its own
+#ifndef TT_LEAF_REFILL_MIN
+#define TT_LEAF_REFILL_MIN TT_REFILL_MIN
+#endif
+
 namespace {
 // :229-241 + set() CommonData.cginc:430-434: the hit record and _PrimaryTriangleInfo of a finished
 // ray (wr = the world-space ray, ray2). Returns whether the ray hit something.
-template <int INFO>
+// LEAF (the leaf-TLAS kernels): best.mesh_id is not kept. A ray that hit anything hit the launch's one instance
+// (inst_mesh / inst_tri_offset, wave-uniform); one that did not has tri_id -1 and mesh 0 as ever. LEAF == 1:
+// wr is not kept either, and the bounce forms that need the world ray re-read it from RayData words 0-1, which
+// a trace never writes.
+template <int INFO, int LEAF = 0>
 __device__ __forceinline__ bool write_record(const TraceArgs& A, uint32_t ray_index, uint32_t pix, float col_w,
-                                             const Best& best, const LaneRay& wr) {
+                                             const Best& best, const LaneRay& wr, int32_t inst_mesh = 0,
+                                             int32_t inst_tri_offset = 0) {
     tt_ray_data* R = A.rays + ray_index;
+    const int32_t best_mesh = LEAF ? (best.tri_id != -1 ? inst_mesh : 0) : best.mesh_id;
+    auto tri_offset_of_best = [&]() -> int32_t {
+        if (LEAF) return best.tri_id != -1 ? inst_tri_offset : A.mesh[0].TriOffset;
+        return A.mesh[best.mesh_id].TriOffset;
+    };
     if (INFO != 0) {
         // (pix % W, pix / W) with pix / W < H is the texel at index pix: no division needed
         if (pix < A.n_pixels) {
             uint4 o;
             bool write = false;
             if (INFO == 1) {
-                const int32_t to = A.mesh[best.mesh_id].TriOffset;
-                o = make_uint4((uint32_t)best.mesh_id, (uint32_t)(best.tri_id - to),
+                const int32_t to = tri_offset_of_best();
+                o = make_uint4((uint32_t)best_mesh, (uint32_t)(best.tri_id - to),
                                __float_as_uint(best.u), __float_as_uint(best.v));
                 write = true;
             } else {
@@ -39,18 +54,31 @@ __device__ __forceinline__ bool write_record(const TraceArgs& A, uint32_t ray_in
                     write = true;
                     const bool miss = best.t == A.far_plane;
                     if ((A.flags & TT_TRACE_USE_RESTIRGI) && !miss) {
-                        const int32_t to = A.mesh[best.mesh_id].TriOffset;
-                        o.x = (uint32_t)best.mesh_id;
+                        const int32_t to = tri_offset_of_best();
+                        o.x = (uint32_t)best_mesh;
                         o.y = (uint32_t)(best.tri_id - to);
                         o.z = (uint32_t)(best.u * 65535.0f) | ((uint32_t)(best.v * 65535.0f) << 16);
-                    } else if ((A.flags & TT_TRACE_USE_ASVGF) || !miss) {
-                        o.x = __float_as_uint(wr.dx);
-                        o.y = __float_as_uint(wr.dy);
-                        o.z = __float_as_uint(wr.dz);
                     } else {
-                        o.x = __float_as_uint(wr.dx * best.t + wr.ox);
-                        o.y = __float_as_uint(wr.dy * best.t + wr.oy);
-                        o.z = __float_as_uint(wr.dz * best.t + wr.oz);
+                        LaneRay w = wr;
+                        if (LEAF == 1) {
+                            const uint4* rp = reinterpret_cast<const uint4*>(R);
+                            const uint4 r0 = rp[0], r1 = rp[1];
+                            w.ox = __uint_as_float(r0.x);
+                            w.oy = __uint_as_float(r0.y);
+                            w.oz = __uint_as_float(r0.z);
+                            w.dx = __uint_as_float(r1.x);
+                            w.dy = __uint_as_float(r1.y);
+                            w.dz = __uint_as_float(r1.z);
+                        }
+                        if ((A.flags & TT_TRACE_USE_ASVGF) || !miss) {
+                            o.x = __float_as_uint(w.dx);
+                            o.y = __float_as_uint(w.dy);
+                            o.z = __float_as_uint(w.dz);
+                        } else {
+                            o.x = __float_as_uint(w.dx * best.t + w.ox);
+                            o.y = __float_as_uint(w.dy * best.t + w.oy);
+                            o.z = __float_as_uint(w.dz * best.t + w.oz);
+                        }
                     }
                     o.w = miss ? 1u : 0u;
                 }
@@ -59,7 +87,7 @@ __device__ __forceinline__ bool write_record(const TraceArgs& A, uint32_t ray_in
         }
     }
     const uint32_t uv = (uint32_t)(best.u * 65535.0f) | ((uint32_t)(best.v * 65535.0f) << 16);
-    const uint4 hit = make_uint4((uint32_t)best.mesh_id, (uint32_t)best.tri_id, __float_as_uint(best.t), uv);
+    const uint4 hit = make_uint4((uint32_t)best_mesh, (uint32_t)best.tri_id, __float_as_uint(best.t), uv);
     reinterpret_cast<uint4*>(R)[2] = hit;
     if (A.hits_out) {  // the compact record stream (multi-GPU gather): a raw buffer store, 32-bit offset
         const u32x4 v = {hit.x, hit.y, hit.z, hit.w};
@@ -139,9 +167,32 @@ __device__ __forceinline__ bool root_leaf_hit(const RootLeaf& R, const LaneRay& 
 // (tt_trace_kernel_indirect), so the direct launches keep exactly their code and kernel names.
 // ORD: TT_TRACE_ADAPTIVE_ORDER (tt_trace_kernel_ord): chunks are dequeued in A.order (when set) and
 // every ray's Reps count goes into the tile cost map.
-template <bool STATS, bool MATCHECK, int INFO, bool IND, bool ORD>
+// LEAF: the leaf-TLAS form (tt_trace_leaf_kernel<IND, INFO>) for launches whose TLAS root
+// is one leaf holding one instance (root_one_instance; C2, C3, C5). Every ray that hits the root's box switches
+// to the same BLAS through the same LeafMesh record and never leaves it (the switch pushes nothing, so the
+// BLAS-exit test `stack_size == tlas_ss` could only hold at stack_size 0, where the ray finishes). The record
+// is read once per wave at a wave-uniform address (scalar loads; from device memory at every launch, so
+// tt_scene_update_meshdata is honoured as in the generic kernel), the offsets and the mesh id are wave-uniform,
+// and no lane keeps tlas_ss, best.mesh_id or (LEAF == 1; LEAF == 2 keeps it for the INFO = 2 record) the world
+// ray: fewer VGPRs (more resident waves), a cheaper ray start, no TLAS-leaf test after a node step and no
+// BLAS-exit test in the advance. The arithmetic of a ray and its order are the generic kernel's, so results are
+// bit-identical. Never with STATS, MATCHECK or ORD.
+template <bool STATS, bool MATCHECK, int INFO, bool IND, bool ORD, int LEAF = 0>
 __device__ __forceinline__ void trace_body(const TraceArgs& A) {
+    static_assert(!LEAF || (!STATS && !MATCHECK && !ORD), "the leaf-TLAS form has no stats / material / order variants");
     __shared__ uint2 s_stack[TT_LDS_STACK][TT_BLOCK];
+    // (read before the kernel's first store, so the compiler can prove the loads unclobbered and make them scalar)
+    float4 L0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), L1 = L0, L2 = L0;  // LEAF: W2L rows of the one instance
+    int4 L4 = make_int4(0, 0, 0, 0);                                     // TriOffset, NodeOffset, MatOffset, BLAS root
+    int32_t L_mesh = 0;                                                  // mesh id
+    if (LEAF) {
+        const float4* mp = reinterpret_cast<const float4*>(A.leaf + (A.root.base_tri + firstbithigh(A.root.bits)));
+        L0 = mp[0];
+        L1 = mp[1];
+        L2 = mp[2];
+        L4 = reinterpret_cast<const int4*>(mp)[3];
+        L_mesh = reinterpret_cast<const int4*>(mp)[4].x;
+    }
     const uint32_t tid = threadIdx.x;
     zero_next_control(A.ctl_next, tid);
     const uint32_t gtid = blockIdx.x * TT_BLOCK + tid;
@@ -185,6 +236,12 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     uint32_t oct = 0;
     int32_t stack_size = 0, tlas_ss = -1;
     int32_t NodeOffset = 0, TriOffset = 0, MatOffset = 0, mesh_id = -1, Reps = 0;
+    if (LEAF) {  // wave-uniform for the whole launch
+        NodeOffset = L4.y;
+        TriOffset = L4.x;
+        MatOffset = L4.z;
+        mesh_id = L_mesh;
+    }
     uint32_t c_nodes = 0, c_tris = 0, c_blas = 0, c_acc = 0, c_rays = 0, c_hits = 0, c_reps = 0, c_ovf = 0;
     uint32_t d_iter = 0, d_node_lanes = 0, d_node_iters = 0, d_tri_lanes = 0, d_tri_iters = 0, d_active_lanes = 0;
     uint32_t d_lead_same = 0, d_uniform = 0;  // node-step uniformity (lanes sharing the first lane's node)
@@ -236,11 +293,13 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     };
     // :229-241: the finished ray's hit record and _PrimaryTriangleInfo
     auto finish_ray = [&]() {
-        const bool hit = write_record<INFO>(A, ray_index, pix, col_w, best, world_ray());
+        const bool hit = write_record<INFO, LEAF>(A, ray_index, pix, col_w, best, world_ray(), mesh_id, TriOffset);
         if (STATS) c_hits += hit ? 1u : 0u;
         (void)hit;
         if (ORD) record_chunk_cost(A, swizzle, ray_index, Reps);
     };
+    // (the leaf form's ray start is cheaper, so its refill threshold is a knob of its own)
+    constexpr uint32_t REFILL_MIN = LEAF ? TT_LEAF_REFILL_MIN : TT_REFILL_MIN;
     while (true) {
         TT_DB(0);
         // ---------------------------------------------------------------- refill
@@ -256,7 +315,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
         // the queue is dry and the live rays fit in 2-lane groups: cooperative drain (tt_wide.h)
         const bool to_wide = TT_WIDE && pool_dry && n_idle < TT_WAVE && TT_WAVE - n_idle <= TT_WIDE_ENTER;
         // finished rays write their records in batches, right before their lanes are refilled
-        if ((n_idle == TT_WAVE && pool_dry) || (n_idle >= TT_REFILL_MIN && !pool_dry) || to_wide) {
+        if ((n_idle == TT_WAVE && pool_dry) || (n_idle >= REFILL_MIN && !pool_dry) || to_wide) {
             if (pending) {
                 TT_DB(1);
                 finish_ray();
@@ -269,9 +328,9 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
             TT_DB(13);
             WideState st{ray, world_ray(), best, cg, tg, oct, stack_size, tlas_ss, NodeOffset, TriOffset, MatOffset,
                          mesh_id, Reps, ray_index, pix, col_w, tid, gtid, (int32_t)tg.y >= 0};
-            regroup<2>(st, __ballot((int32_t)tg.y >= 0), lane);
+            regroup<2, LEAF>(st, __ballot((int32_t)tg.y >= 0), lane);
             auto finish_wide = [&](const WideState& w) {
-                const bool hit = write_record<INFO>(A, w.ray_index, w.pix, w.col_w, w.best, w.wray);
+                const bool hit = write_record<INFO, LEAF>(A, w.ray_index, w.pix, w.col_w, w.best, w.wray, mesh_id, TriOffset);
                 if (STATS) c_hits += hit ? 1u : 0u;
                 if (ORD) record_chunk_cost(A, swizzle, w.ray_index, w.Reps);
             };
@@ -279,13 +338,13 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                 keep_record(A, w.ray_index);
                 if (ORD) record_chunk_cost(A, swizzle, w.ray_index, w.Reps);
             };
-            wide_phase<STATS, MATCHECK, 2>(A, st, s_stack, spill, spill_stride, nodes, tris, lane,
+            wide_phase<STATS, MATCHECK, 2, LEAF>(A, st, s_stack, spill, spill_stride, nodes, tris, lane,
                                            Counters{c_nodes, c_tris, c_blas, c_acc, c_hits, c_reps, c_ovf},
                                            finish_wide, exhaust_wide);
             break;
         }
 #endif
-        if (n_idle >= TT_REFILL_MIN && !pool_dry) {
+        if (n_idle >= REFILL_MIN && !pool_dry) {
             TT_DB(2);
 #if TT_LONG_PRIO
             // a wave carrying a long ray (>= TT_LONG_PRIO node steps so far) issues ahead of the others until
@@ -347,25 +406,49 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                 ray.ix = rcp_rn(ray.dx);
                 ray.iy = rcp_rn(ray.dy);
                 ray.iz = rcp_rn(ray.dz);
-                wray = ray;
-                oct = octant_inv4(ray);
                 best.t = A.far_plane;
                 best.u = 0.0f;
                 best.v = 0.0f;
                 best.mesh_id = 0;
                 best.tri_id = -1;
-                cg = make_uint2(A.tlas_base, 0x80000000u);  // the TLAS root: node 0 of the context's TLAS
                 tg = make_uint2(0u, 0u);
                 stack_size = 0;
-                tlas_ss = -1;
-                NodeOffset = (int32_t)A.tlas_base;  // TLAS level (0, or a frame-slot TLAS's region)
-                TriOffset = 0;
-                MatOffset = 0;
-                mesh_id = -1;
-                Reps = 0;
+                if (LEAF) {
+                    if (LEAF == 2) wray = ray;
+                    // the root's node step; a hit is the TLAS leaf -> BLAS switch (enter_blas with nothing to
+                    // push), a miss leaves an empty group: the advance below finishes the ray with the miss record
+                    cg = make_uint2(0u, 0u);
+                    Reps = 1;
+                    if (root_leaf_hit(A.root, ray, best.t)) {
+                        LaneRay nr;
+                        nr.dx = fma_(L0.z, ray.dz, fma_(L0.y, ray.dy, L0.x * ray.dx));
+                        nr.dy = fma_(L1.z, ray.dz, fma_(L1.y, ray.dy, L1.x * ray.dx));
+                        nr.dz = fma_(L2.z, ray.dz, fma_(L2.y, ray.dy, L2.x * ray.dx));
+                        nr.ox = fma_(L0.z, ray.oz, fma_(L0.y, ray.oy, L0.x * ray.ox)) + L0.w;
+                        nr.oy = fma_(L1.z, ray.oz, fma_(L1.y, ray.oy, L1.x * ray.ox)) + L1.w;
+                        nr.oz = fma_(L2.z, ray.oz, fma_(L2.y, ray.oy, L2.x * ray.ox)) + L2.w;
+                        nr.ix = rcp_rn(nr.dx);
+                        nr.iy = rcp_rn(nr.dy);
+                        nr.iz = rcp_rn(nr.dz);
+                        ray = nr;
+                        oct = octant_inv4(ray);
+                        cg = make_uint2((uint32_t)L4.w, 0x80000000u);
+                    }
+                }
+                if (!LEAF) {
+                    wray = ray;
+                    oct = octant_inv4(ray);
+                    cg = make_uint2(A.tlas_base, 0x80000000u);  // the TLAS root: node 0 of the context's TLAS
+                    tlas_ss = -1;
+                    NodeOffset = (int32_t)A.tlas_base;  // TLAS level (0, or a frame-slot TLAS's region)
+                    TriOffset = 0;
+                    MatOffset = 0;
+                    mesh_id = -1;
+                    Reps = 0;
+                }
                 if (STATS) c_rays++;
 #if TT_ROOT_LEAF
-                if (rl_ok) {  // the root's node step, then the TLAS leaf -> BLAS switch
+                if (!LEAF && rl_ok) {  // the root's node step, then the TLAS leaf -> BLAS switch
                     const RootLeaf& RL = A.root;
                     const bool hit = root_leaf_hit(RL, ray, best.t);
                     cg = make_uint2(RL.base_child, 0u);  // (hitmask & 0xff000000) | imask: both 0
@@ -442,7 +525,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                 tg = cg;
                 cg = make_uint2(0u, 0u);
             }
-            if ((int32_t)tg.y > 0 && tlas_ss == -1) enter_blas();  // :194-219 TLAS leaf -> BLAS
+            if (!LEAF && (int32_t)tg.y > 0 && tlas_ss == -1) enter_blas();  // :194-219 TLAS leaf -> BLAS
         }
 
         if (STATS) {
@@ -473,7 +556,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
             TT_DB(10);
             if (stack_size != 0) {
                 TT_DB(11);
-                if (stack_size == tlas_ss) {
+                if (!LEAF && stack_size == tlas_ss) {
                     TT_DB(12);
                     NodeOffset = (int32_t)A.tlas_base;
                     TriOffset = 0;
@@ -530,10 +613,40 @@ template <int INFO>
 __global__ TT_BOUNDS void tt_trace_kernel_ord_mat(TraceArgs A) {
     trace_body<false, true, INFO, false, true>(A);
 }
+// The leaf-TLAS form (trace_body<LEAF>): its own kernels, so the generic ones keep their code and names.
+// Waves per SIMD the register allocation is held to. 6 for every INFO form (73 / 78 / 80 VGPRs, no scratch):
+// INFO 0 / 1 also fit 7 waves (71 / 72 VGPRs, no scratch), but the smaller SGPR budget at 7 waves costs 7 / 14
+// SGPR spills inside the loop and measured 1.2 % slower on the headline. A 5-wave bound measured 2.7 % slower:
+// the sixth resident wave is where the gain over the generic kernels (89 / 93 VGPRs, 5 waves) comes from, the
+// VALU instructions per ray barely move (profiles/r07/leaf/). Capping one launch's grid at 5
+// waves per SIMD (TT_BLOCKS_PER_CU=20) costs nothing while other frame slots' launches fill the SIMDs.
+#ifndef TT_LEAF_WAVES
+#define TT_LEAF_WAVES(INFO) 6
+#endif
+#define TT_LEAF_BOUNDS __launch_bounds__(TT_BLOCK) __attribute__((amdgpu_waves_per_eu(TT_LEAF_WAVES(INFO))))
+// TT_LEAF_WRAY_RESIDENT 1: INFO = 2 keeps the world ray's origin and direction in registers (80 VGPRs, still
+// 6 waves, no scratch); 0: it re-reads them from RayData for the record (77 VGPRs), measured 1.5 % slower on the
+// headline (profiles/r07/leaf/ab.json)
+#ifndef TT_LEAF_WRAY_RESIDENT
+#define TT_LEAF_WRAY_RESIDENT 1
+#endif
+#define TT_LEAF_FORM(INFO) ((INFO) == 2 && TT_LEAF_WRAY_RESIDENT ? 2 : 1)
+// (IND, INFO: the profile summaries bench.py reads key a kernel by its name's last template argument, INFO)
+template <bool IND, int INFO>
+__global__ TT_LEAF_BOUNDS void tt_trace_leaf_kernel(TraceArgs A) {
+    trace_body<false, false, INFO, IND, false, TT_LEAF_FORM(INFO)>(A);
+}
 
 // ------------------------------------------------------------------ launchers
 template <bool S, bool M, int I>
-static hipError_t launch_one(const TraceArgs& a, uint32_t grid, hipStream_t st) {
+static hipError_t launch_one(const TraceArgs& a, bool leaf, uint32_t grid, hipStream_t st) {
+    if constexpr (!S && !M) {
+        if (leaf) {  // never with stats, the material check or the adaptive order (tt_api.hip decides)
+            if (a.n_rays_dev) hipLaunchKernelGGL((tt_trace_leaf_kernel<true, I>), dim3(grid), dim3(TT_BLOCK), 0, st, a);
+            else hipLaunchKernelGGL((tt_trace_leaf_kernel<false, I>), dim3(grid), dim3(TT_BLOCK), 0, st, a);
+            return hipGetLastError();
+        }
+    }
     if constexpr (!S) {
         if (a.n_rays_dev) {  // stats launches never take a device count (tt_api.hip refuses them)
             hipLaunchKernelGGL((tt_trace_kernel_indirect<M, I>), dim3(grid), dim3(TT_BLOCK), 0, st, a);
@@ -550,16 +663,20 @@ static hipError_t launch_one(const TraceArgs& a, uint32_t grid, hipStream_t st) 
 }
 
 template <bool S, bool M>
-static hipError_t launch_info(const TraceArgs& a, int info, uint32_t grid, hipStream_t st) {
-    if (info == 0) return launch_one<S, M, 0>(a, grid, st);
-    if (info == 1) return launch_one<S, M, 1>(a, grid, st);
-    return launch_one<S, M, 2>(a, grid, st);
+static hipError_t launch_info(const TraceArgs& a, int info, bool leaf, uint32_t grid, hipStream_t st) {
+    if (info == 0) return launch_one<S, M, 0>(a, leaf, grid, st);
+    if (info == 1) return launch_one<S, M, 1>(a, leaf, grid, st);
+    return launch_one<S, M, 2>(a, leaf, grid, st);
 }
 
-hipError_t tt_launch_trace(const TraceArgs& a, bool stats, bool matcheck, int info, uint32_t grid,
+// leaf: take the leaf-TLAS kernels (the caller has checked root_one_instance(a.root), no stats, no material
+// check, no adaptive order)
+hipError_t tt_launch_trace(const TraceArgs& a, bool stats, bool matcheck, int info, bool leaf, uint32_t grid,
                            hipStream_t st) {
-    if (stats) return matcheck ? launch_info<true, true>(a, info, grid, st) : launch_info<true, false>(a, info, grid, st);
-    return matcheck ? launch_info<false, true>(a, info, grid, st) : launch_info<false, false>(a, info, grid, st);
+    if (leaf && (stats || matcheck || a.chunk_cost || !root_one_instance(a.root))) return hipErrorInvalidValue;
+    if (stats)
+        return matcheck ? launch_info<true, true>(a, info, false, grid, st) : launch_info<true, false>(a, info, false, grid, st);
+    return matcheck ? launch_info<false, true>(a, info, false, grid, st) : launch_info<false, false>(a, info, leaf, grid, st);
 }
 
 // Occupancy (resident blocks per CU) of every instantiation: they differ in registers, so each
@@ -577,8 +694,15 @@ static int occ_ord() {
                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, tt_trace_kernel_ord<I>, TT_BLOCK, 0);
     return e == hipSuccess ? b : 1;
 }
-// index = stats*6 + matcheck*3 + info; 12 + matcheck*3 + info: the adaptive-order kernels
-hipError_t tt_trace_occupancy_table(int* out18) {
+template <bool IND, int I>
+static int occ_leaf() {
+    int b = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, tt_trace_leaf_kernel<IND, I>, TT_BLOCK, 0) == hipSuccess ? b : 1;
+}
+// index = stats*6 + matcheck*3 + info; 12 + matcheck*3 + info: the adaptive-order kernels;
+// 18 + indirect*3 + info: the leaf-TLAS kernels
+hipError_t tt_trace_occupancy_table(int* out24) {
+    int* out18 = out24;
     int* out12 = out18;
     out12[0] = occ_one<false, false, 0>();
     out12[1] = occ_one<false, false, 1>();
@@ -598,6 +722,12 @@ hipError_t tt_trace_occupancy_table(int* out18) {
     out18[15] = occ_ord<true, 0>();
     out18[16] = occ_ord<true, 1>();
     out18[17] = occ_ord<true, 2>();
+    out24[18] = occ_leaf<false, 0>();
+    out24[19] = occ_leaf<false, 1>();
+    out24[20] = occ_leaf<false, 2>();
+    out24[21] = occ_leaf<true, 0>();
+    out24[22] = occ_leaf<true, 1>();
+    out24[23] = occ_leaf<true, 2>();
     return hipGetLastError();
 }
 

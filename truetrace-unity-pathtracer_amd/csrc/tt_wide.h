@@ -62,7 +62,10 @@ __device__ __forceinline__ void shfl_ray(LaneRay& r, uint32_t src) {
 
 // Regroups the rays led by the lanes in `lead` (wave-uniform) into groups of GN consecutive lanes.
 // Must run with every lane of the wave enabled (ds_bpermute reads inactive lanes as zero).
-template <int GN>
+// LEAF (the leaf-TLAS kernels, tt_trace.hip; 1: the world ray is re-read where needed, 2: it stays resident):
+// tlas_ss, best.mesh_id and, in form 1, wray are not part of a ray's state and the four instance words are
+// wave-uniform, so none of them moves.
+template <int GN, int LEAF = 0>
 __device__ __forceinline__ void regroup(WideState& s, uint64_t lead, uint32_t lane) {
     const uint32_t grp = lane / GN;
     uint32_t src = 0;
@@ -77,11 +80,11 @@ __device__ __forceinline__ void regroup(WideState& s, uint64_t lead, uint32_t la
         }
     }
     shfl_ray(s.ray, src);
-    shfl_ray(s.wray, src);
+    if (LEAF != 1) shfl_ray(s.wray, src);
     s.best.t = shfl_f(s.best.t, src);
     s.best.u = shfl_f(s.best.u, src);
     s.best.v = shfl_f(s.best.v, src);
-    s.best.mesh_id = shfl_i(s.best.mesh_id, src);
+    if (!LEAF) s.best.mesh_id = shfl_i(s.best.mesh_id, src);
     s.best.tri_id = shfl_i(s.best.tri_id, src);
     s.cg.x = shfl_u(s.cg.x, src);
     s.cg.y = shfl_u(s.cg.y, src);
@@ -89,11 +92,13 @@ __device__ __forceinline__ void regroup(WideState& s, uint64_t lead, uint32_t la
     s.tg.y = shfl_u(s.tg.y, src);
     s.oct = shfl_u(s.oct, src);
     s.stack_size = shfl_i(s.stack_size, src);
-    s.tlas_ss = shfl_i(s.tlas_ss, src);
-    s.NodeOffset = shfl_i(s.NodeOffset, src);
-    s.TriOffset = shfl_i(s.TriOffset, src);
-    s.MatOffset = shfl_i(s.MatOffset, src);
-    s.mesh_id = shfl_i(s.mesh_id, src);
+    if (!LEAF) {
+        s.tlas_ss = shfl_i(s.tlas_ss, src);
+        s.NodeOffset = shfl_i(s.NodeOffset, src);
+        s.TriOffset = shfl_i(s.TriOffset, src);
+        s.MatOffset = shfl_i(s.MatOffset, src);
+        s.mesh_id = shfl_i(s.mesh_id, src);
+    }
     s.Reps = shfl_i(s.Reps, src);
     s.ray_index = shfl_u(s.ray_index, src);
     s.pix = shfl_u(s.pix, src);
@@ -179,7 +184,9 @@ __device__ __forceinline__ uint32_t node_intersect_part(const uint4 n0, const ui
 // returns when every ray of the wave has finished. `finish(st)` writes a finished ray's records,
 // `exhaust(st)` sees a ray that ends without a record (the Reps bound or a stack overflow: the
 // reference writes nothing for it); both are called on the group's first lane only.
-template <bool STATS, bool MATCHECK, int G, class Finish, class Exhaust>
+// LEAF: every ray is inside the one instance's BLAS for good (st.NodeOffset / TriOffset / MatOffset hold the
+// instance's wave-uniform values): no TLAS leaf -> BLAS switch and no BLAS exit.
+template <bool STATS, bool MATCHECK, int G, int LEAF, class Finish, class Exhaust>
 __device__ void wide_phase(const TraceArgs& A, WideState& st, uint2 (*s_stack)[TT_BLOCK], uint2* __restrict__ spill,
                            uint32_t spill_stride, __amdgpu_buffer_rsrc_t nodes, __amdgpu_buffer_rsrc_t tris,
                            uint32_t lane, Counters C, Finish& finish, Exhaust& exhaust) {
@@ -194,8 +201,8 @@ __device__ void wide_phase(const TraceArgs& A, WideState& st, uint2 (*s_stack)[T
         TT_DB(G == 2 ? 14 : G == 4 ? 15 : 16);
         if constexpr (G < 8) {
             if (n * (2 * G) <= TT_WAVE) {
-                regroup<2 * G>(st, lead, lane);
-                wide_phase<STATS, MATCHECK, 2 * G>(A, st, s_stack, spill, spill_stride, nodes, tris, lane, C, finish,
+                regroup<2 * G, LEAF>(st, lead, lane);
+                wide_phase<STATS, MATCHECK, 2 * G, LEAF>(A, st, s_stack, spill, spill_stride, nodes, tris, lane, C, finish,
                                                    exhaust);
                 return;
             }
@@ -241,7 +248,7 @@ __device__ void wide_phase(const TraceArgs& A, WideState& st, uint2 (*s_stack)[T
                 st.tg = st.cg;
                 st.cg = make_uint2(0u, 0u);
             }
-            if (st.active && st.tg.y != 0u && st.tlas_ss == -1) {  // :194-219 TLAS leaf -> BLAS
+            if (!LEAF && st.active && st.tg.y != 0u && st.tlas_ss == -1) {  // :194-219 TLAS leaf -> BLAS
                 const uint32_t mo = firstbithigh(st.tg.y);
                 st.tg.y &= ~(1u << mo);
                 const float4* mp = reinterpret_cast<const float4*>(A.leaf + (st.tg.x + mo));  // LeafMesh
@@ -323,7 +330,7 @@ __device__ void wide_phase(const TraceArgs& A, WideState& st, uint2 (*s_stack)[T
                 st.best.u = shfl_f(c.u, src);
                 st.best.v = shfl_f(c.v, src);
                 st.best.tri_id = shfl_i(tri_id, src);
-                st.best.mesh_id = st.mesh_id;
+                if (!LEAF) st.best.mesh_id = st.mesh_id;
             }
 #pragma unroll
             for (uint32_t k = 0; k < (uint32_t)G; k++)
@@ -333,7 +340,7 @@ __device__ void wide_phase(const TraceArgs& A, WideState& st, uint2 (*s_stack)[T
         // ----------------------------------------- advance: pop / finish (:228-251)
         if (st.active && st.tg.y == 0u && (st.cg.y & 0xff000000u) == 0u) {
             if (stack_size != 0) {
-                if (stack_size == st.tlas_ss) {
+                if (!LEAF && stack_size == st.tlas_ss) {
                     st.NodeOffset = (int32_t)A.tlas_base;
                     st.TriOffset = 0;
                     st.tlas_ss = -1;

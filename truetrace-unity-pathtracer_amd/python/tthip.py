@@ -43,6 +43,10 @@ TT_TRACE_ASYNC = 1 << 4
 TT_TRACE_IGNORE_GLASS = 1 << 5       # IgnoreGlassMain (IntersectionKernels.compute:42-44)
 TT_TRACE_IGNORE_BACKFACING = 1 << 6  # IgnoreBackfacing (IntersectionKernels.compute:45-47)
 TT_TRACE_ADAPTIVE_ORDER = 1 << 7  # dequeue the previous launch's costliest tiles first (tt_order.hip)
+# tt_trace_last_form: which closest-hit kernel form a context's last trace launch took
+TT_TRACE_FORM_NONE, TT_TRACE_FORM_GENERIC, TT_TRACE_FORM_LEAF = 0, 1, 2
+# tt_tlas_root_form: what a TLAS's node 0 is (2: one leaf of one instance, the leaf-TLAS kernels' condition)
+TT_ROOT_GENERIC, TT_ROOT_ONE_LEAF, TT_ROOT_ONE_INSTANCE = 0, 1, 2
 TT_SHADOW_RADIANCE_CACHE = 1 << 7    # RadianceCache define (GlobalDefines.cginc:15) for tt_trace_shadow_ex
 TT_SHADOW_VISIBILITY_CHECK = 1 << 8  # VisabilityCheckCompute semantics (CommonData.cginc:710-819)
 TT_STACK_SIZE = 16
@@ -319,6 +323,10 @@ def hip_lib():
         L.tt_scene_validate.restype = i32
         L.tt_trace_diagnostics.argtypes = [vp, vp]
         L.tt_trace_diagnostics.restype = i32
+        L.tt_trace_last_form.argtypes = [vp, C.POINTER(u32)]
+        L.tt_trace_last_form.restype = i32
+        L.tt_tlas_root_form.argtypes = [vp, C.POINTER(u32)]
+        L.tt_tlas_root_form.restype = i32
         L.tt_selftest_rcp.argtypes = [vp, vp]
         L.tt_selftest_rcp.restype = i32
         L.tt_timing_reset.argtypes = [vp]
@@ -693,6 +701,15 @@ def camera_rays_host(cam_to_world: np.ndarray, cam_inv_proj: np.ndarray, width: 
 
 
 # ---------------------------------------------------------------- engine
+def tlas_root_form(node0) -> int:
+    """tt_tlas_root_form of one 80-byte node (any contiguous array holding node 0 first); needs no device."""
+    f = C.c_uint32()
+    st = hip_lib().tt_tlas_root_form(_ptr(node0), C.byref(f))
+    if st != TT_OK:
+        raise TTError(st, "tt_tlas_root_form")
+    return int(f.value)
+
+
 class Engine:
     """One context per GPU (tt_ctx_create). ``trace`` is the kernel_trace dispatch."""
 
@@ -832,6 +849,12 @@ class Engine:
         keys = ["iterations", "node_iters", "node_lanes", "tri_iters", "tri_lanes", "active_lanes", "lead_same_lanes",
                 "uniform_node_iters"]
         return {k: int(v) for k, v in zip(keys, d)}
+
+    def last_trace_form(self) -> int:
+        """tt_trace_last_form: TT_TRACE_FORM_GENERIC or TT_TRACE_FORM_LEAF for the context's last trace launch."""
+        f = C.c_uint32()
+        self._check(self.L.tt_trace_last_form(self.h, C.byref(f)), "tt_trace_last_form")
+        return int(f.value)
 
     def selftest_rcp(self) -> int:
         """Inputs (of all 2^32 fp32 bit patterns) where the kernels' fast reciprocal differs from the
