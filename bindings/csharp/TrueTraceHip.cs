@@ -95,6 +95,18 @@ namespace TrueTrace.Hip
     public enum TTGroupFlags : uint { None = 0, CopyGather = 1u << 0, Bounce = 1u << 1, Info = 1u << 2 }
 
     /// tt_group_config: the screen a multi-GPU group traces, its tile edge, frames in flight and flags.
+    /// TerrainDat / TerrainData, 60 B (CommonVars.cs:147-157, CommonData.cginc:280-287).
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct TtTerrain
+    {
+        public fixed float positionOffset[3];
+        public float heightScale;
+        public fixed float terrainDim[2];
+        public fixed float alphaMap[4];
+        public fixed float heightMap[4];  // xy: atlas uv of the terrain's uv = 1 corner, zw: of its uv = 0 corner
+        public int matOffset;
+    }
+
     [StructLayout(LayoutKind.Sequential)]
     public struct TTGroupConfig
     {
@@ -170,6 +182,21 @@ namespace TrueTrace.Hip
         // _TextureAtlas decoded to RGBA half (4 x ushort per texel), for the stained-glass shadow tint.
         [DllImport(Lib)] public static extern unsafe TTStatus tt_scene_upload_texture_atlas(IntPtr ctx, ushort* rgbaHalf,
             uint width, uint height);
+        // Terrains + the Heightmap atlas (AssetManager.cs:90-93): binary16 texels; n == 0 clears the set.
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_scene_upload_terrains(IntPtr ctx, TtTerrain* terrains, uint n,
+            ushort* heightmapHalf, uint width, uint height);
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_terrain_validate(TtTerrain* terrains, uint n,
+            ushort* heightmapHalf, uint width, uint height, byte* why, uint whyLen);
+        // kernel_heightmap / kernel_shadow_heightmap (IntersectionKernels.compute:508-710); pointers are host or HIP
+        // device memory as the flags say (TT_TRACE_DEVICE_PTRS); the _indirect forms read their count on the device.
+        [DllImport(Lib)] public static extern TTStatus tt_trace_heightmap(IntPtr ctx, ref TTTraceParams p, IntPtr globalRays,
+            IntPtr primaryInfo, out TTStats stats);
+        [DllImport(Lib)] public static extern TTStatus tt_trace_heightmap_indirect(IntPtr ctx, ref TTTraceParams p,
+            IntPtr nRaysDev, IntPtr globalRays, IntPtr primaryInfo);
+        [DllImport(Lib)] public static extern TTStatus tt_trace_shadow_heightmap(IntPtr ctx, ref TTShadowParams p,
+            IntPtr shadowRays, IntPtr visibility, IntPtr globalColors, IntPtr neePos, IntPtr cacheBuffer);
+        [DllImport(Lib)] public static extern TTStatus tt_trace_shadow_heightmap_indirect(IntPtr ctx, ref TTShadowParams p,
+            IntPtr nRaysDev, IntPtr shadowRays, IntPtr visibility, IntPtr globalColors, IntPtr neePos, IntPtr cacheBuffer);
         // RefitTLAS: MeshAABBs as {BBMax.xyz, BBMin.xyz} per mesh; flags: TT_TRACE_DEVICE_PTRS / ASYNC.
         [DllImport(Lib)] public static extern unsafe TTStatus tt_tlas_refit(IntPtr ctx, uint nTlasNodes, float* meshAabbs,
             uint nMesh, uint flags);
@@ -560,6 +587,56 @@ namespace TrueTrace.Hip
         {
             fixed (ushort* t = rgbaHalf)
                 Check(Native.tt_scene_upload_texture_atlas(m_ctx, t, (uint)width, (uint)height));
+        }
+
+        /// The Terrains / Heightmap bindings (AssetManager.cs:90-93): TerrainData records and the RHalf heightmap
+        /// atlas read back as binary16 texels, once per scene change. An empty array clears the set.
+        public unsafe void SetTerrains(TtTerrain[] terrains, ushort[] heightmapHalf, int width, int height)
+        {
+            fixed (TtTerrain* t = terrains) fixed (ushort* h = heightmapHalf)
+                Check(Native.tt_scene_upload_terrains(m_ctx, t, (uint)(terrains?.Length ?? 0), h, (uint)width, (uint)height));
+        }
+
+        /// One kernel_heightmap dispatch (RayTracingMaster.cs:973-977) on HIP device buffers, right after the
+        /// trace of the same bounce: terrain hits rewrite GlobalRays[].hits and _PrimaryTriangleInfo in place.
+        public TTStats TraceHeightmapDevice(IntPtr globalRays, uint nRays, int curBounce, float farPlane, int width,
+                                            int height, IntPtr primaryInfo = default, TTTraceFlags flags = 0,
+                                            bool async = false)
+        {
+            var p = new TTTraceParams { nRays = nRays, bounce = curBounce, farPlane = farPlane, screenWidth = (uint)width,
+                                        screenHeight = (uint)height,
+                                        flags = flags | TTTraceFlags.DevicePtrs | (async ? TTTraceFlags.Async : 0) };
+            Check(Native.tt_trace_heightmap(m_ctx, ref p, globalRays, primaryInfo, out TTStats s));
+            return s;
+        }
+
+        /// The same with BufferSizes[CurBounce].heighmap_rays on the GPU (no host round trip).
+        public void TraceHeightmapIndirect(IntPtr globalRays, IntPtr nRaysDev, uint capacity, int curBounce, float farPlane,
+                                           int width, int height, IntPtr primaryInfo = default, TTTraceFlags flags = 0)
+        {
+            var p = new TTTraceParams { nRays = capacity, bounce = curBounce, farPlane = farPlane, screenWidth = (uint)width,
+                                        screenHeight = (uint)height, flags = flags | TTTraceFlags.DevicePtrs };
+            Check(Native.tt_trace_heightmap_indirect(m_ctx, ref p, nRaysDev, globalRays, primaryInfo));
+        }
+
+        /// One kernel_shadow_heightmap dispatch (RayTracingMaster.cs:1000-1004) on HIP device buffers, after
+        /// TraceShadowDevice with no accumulation outputs (the reference's TerrainExists form of kernel_shadow).
+        /// nRaysDev != default: the indirect form, nRays is then the capacity.
+        public void TraceShadowHeightmapDevice(IntPtr shadowRays, uint nRays, int curBounce, int width, int height,
+                                               IntPtr visibility = default, IntPtr globalColors = default,
+                                               IntPtr neePos = default, IntPtr cacheBuffer = default,
+                                               TTTraceFlags flags = TTTraceFlags.RadianceCache, bool async = false,
+                                               IntPtr nRaysDev = default)
+        {
+            var p = new TTShadowParams { nRays = nRays, bounce = curBounce, screenWidth = (uint)width,
+                                         screenHeight = (uint)height,
+                                         flags = flags | TTTraceFlags.DevicePtrs | (async ? TTTraceFlags.Async : 0) };
+            if (nRaysDev != IntPtr.Zero)
+                Check(Native.tt_trace_shadow_heightmap_indirect(m_ctx, ref p, nRaysDev, shadowRays, visibility, globalColors,
+                                                                neePos, cacheBuffer));
+            else
+                Check(Native.tt_trace_shadow_heightmap(m_ctx, ref p, shadowRays, visibility, globalColors, neePos,
+                                                       cacheBuffer));
         }
 
         /// AssetManager.RefitTLAS(Boxes, cmd) (AssetManager.cs:1473-1548): re-quantizes the TLAS

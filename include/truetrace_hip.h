@@ -285,6 +285,41 @@ tt_status tt_scene_upload_alpha_atlas(tt_ctx* ctx, const uint8_t* texels, uint32
  * TT_ERR_UNSUPPORTED. */
 tt_status tt_scene_upload_texture_atlas(tt_ctx* ctx, const uint16_t* rgba_half, uint32_t width, uint32_t height);
 
+/* TerrainDat / TerrainData, 60 B (CommonVars.cs:147-157, CommonData.cginc:280-287): one Unity terrain.
+ * The terrain occupies the box PositionOffset + (0 .. TerrainDim.x, 0 .. TerrainDim.x, 0 .. TerrainDim.y);
+ * its surface is y = PositionOffset.y + 0.01 + 2 * HeightScale * Heightmap(uv), uv = (x / TerrainDim.x,
+ * z / TerrainDim.y) mapped into the atlas rectangle HeightMap: atlas_uv = uv * (HeightMap.xy - HeightMap.zw)
+ * + HeightMap.zw (so .zw is the rectangle's corner at uv = 0 and .xy the corner at uv = 1). */
+typedef struct tt_terrain {
+    float PositionOffset[3];
+    float HeightScale;
+    float TerrainDim[2];
+    float AlphaMap[4];   /* not read by the intersection stage */
+    float HeightMap[4];
+    int32_t MatOffset;   /* not read by the intersection stage */
+} tt_terrain;
+TT_STATIC_ASSERT(sizeof(tt_terrain) == 60, "TerrainData is 60 bytes");
+
+/* mesh_id of a terrain hit record (IntersectionKernels.compute:686); its triangle_id is the terrain index. */
+#define TT_TERRAIN_MESH_ID 9999999u
+/* Hard bound of the heightmap ray march per terrain (IntersectionKernels.compute:535, :653). */
+#define TT_TERRAIN_MAX_STEPS 2000
+
+/* Terrains and the Heightmap atlas (AssetManager.cs:90-93; RHalf, :237): n TerrainData records and the atlas
+ * as width*height IEEE binary16 texels, same row orientation as the alpha atlas. Copied to HBM; replaces
+ * any previous set; n == 0 clears it (heightmap_half may then be NULL). The set belongs to the scene like
+ * the atlases: contexts sharing the scene (tt_ctx_share_scene / _blas) see it, the call is refused while
+ * borrowers exist, and a later tt_scene_upload keeps it. Every field must be finite and every HeightMap
+ * rectangle must lie in [0, 1] (TT_ERR_INVALID_ARG, reason in tt_last_error). Filtering is pinned as the
+ * alpha atlas's linear filter, applied to exactly decoded half texels. tt_group_* does not learn terrains:
+ * a host with terrains traces them on the member contexts (tt_group_member_ctx). */
+tt_status tt_scene_upload_terrains(tt_ctx* ctx, const tt_terrain* terrains, uint32_t n,
+                                   const uint16_t* heightmap_half, uint32_t width, uint32_t height);
+/* The check tt_scene_upload_terrains runs (host only, no device needed). why (nullable) receives the first
+ * violation. */
+tt_status tt_terrain_validate(const tt_terrain* terrains, uint32_t n, const uint16_t* heightmap_half,
+                              uint32_t width, uint32_t height, char* why, uint32_t why_len);
+
 /* Per-frame TLAS refit on the GPU: AssetManager.RefitTLAS
  * (AssetManager.cs:1473-1548) with BVHRefitter.compute's RefitBVHLayer / NodeUpdate / NodeCompress
  * (:220-371). Re-quantizes p, e and the child boxes of the uploaded nodes [0, n_tlas_nodes) from
@@ -637,11 +672,65 @@ tt_status tt_trace_shadow_ex_indirect(tt_ctx* ctx, const tt_shadow_params* p, co
                                       tt_shadow_ray* shadow_rays, float* visibility, tt_col_data* global_colors,
                                       float* nee_pos, tt_cache_data* cache_buffer);
 
+/* ------------------------------------------------- terrains (heightmap ray march) */
+/* Replaces one kernel_heightmap dispatch (IntersectionKernels.compute:602-710; RayTracingMaster.cs:973-977):
+ * per-ray sphere tracing against the uploaded terrains, over the rays tt_trace_closest just traced (same
+ * bounce half of GlobalRays, same flags: TT_TRACE_DEVICE_PTRS / _ASYNC / _USE_RESTIRGI / _STATS, same
+ * host-staging rules). For each terrain in order: rayBoxIntersection (:513-521) against the box shrunk by
+ * 0.001 with tMax = the record's t (floor 0.025); from max(t0 + 0.0001, 0) a march of at most
+ * TT_TERRAIN_MAX_STEPS samples while CurDist < t and the position is strictly inside (0, dim.x) x (0, 1000) x
+ * (0, dim.y); on dist < 0.0001 -- after the reference's two-stage bisection (:658-677) when the sample lies
+ * below the surface -- the record becomes (TT_TERRAIN_MESH_ID, terrain index, CurDist + t0, uv packed as set()),
+ * u, v = the last sample's unmapped uv, and the _PrimaryTriangleInfo texel (primary_info nullable) is written
+ * at bounce 0 as (mesh_id, terrain, asuint(u), asuint(v)) and at bounce 1 as (UseReSTIRGI ? origin +
+ * direction * t : direction, 1) (:687-691: no Data.w test, global_colors is not read); the next terrain then
+ * sees the shortened t. Rays that miss keep their record and texel. Numerics: the header's contract, plus
+ * g = sin(atan(1/2)) pinned as the fp32 nearest 1/sqrt(5), length(q) = sqrt(dot(q, q)) correctly rounded,
+ * abs / max(0, q) / all(a < b) as plain IEEE comparisons (NaN compares false), SampleLevel = the pinned
+ * linear filter on exactly decoded half texels. Results are bit-identical to tt_terrain_trace_host
+ * (truetrace_scene.h). With TT_TRACE_STATS: rays, hits (rays whose record was rewritten), node_visits
+ * (heightmap samples taken) and reps_exhausted (marches that ended at the step bound).
+ * TT_ERR_NO_SCENE when no terrain set is uploaded. One launch per terrain, one thread per ray; the
+ * environment variable TT_TERRAIN_FORM=persistent (read once per process) selects the persistent refill form
+ * of the march kernels instead, which measured slower and gives identical results. */
+tt_status tt_trace_heightmap(tt_ctx* ctx, const tt_trace_params* p, tt_ray_data* global_rays,
+                             uint32_t* primary_info, tt_stats* stats);
+/* The same with a device-resident ray count: the contract of tt_trace_closest_indirect. */
+tt_status tt_trace_heightmap_indirect(tt_ctx* ctx, const tt_trace_params* p, const uint32_t* n_rays_dev,
+                                      tt_ray_data* global_rays, uint32_t* primary_info);
+/* Replaces one kernel_shadow_heightmap dispatch (IntersectionKernels.compute:508-600; RayTracingMaster.cs:
+ * 1000-1004). Only rays with t != 0 are marched (max distance |t|, the unshrunken box, from t0 + 0.001; the
+ * loop tests the previous sample's position > 0, as the reference). An occluded ray writes nothing and keeps
+ * its t. A ray no terrain occludes gets the outputs of :573-591, which use illumination without a throughput:
+ *   bounce 0: NEEPosA[pixel] = (origin + direction * |t|, 0);
+ *   TT_SHADOW_RADIANCE_CACHE: CurrentIlluminance = EncodeRGB(DecodeRGB(it) + illumination *
+ *       ((!UseReSTIRGI || t >= 0) ? 1 : unpackRGBE(asuint(LuminanceIncomming))));
+ *   t >= 0: bounce 0: Direct += illumination; else, without TT_SHADOW_RADIANCE_CACHE: Indirect += illumination;
+ *   t <  0: bounce != 0 && UseReSTIRGI: Indirect += illumination;
+ *           else PrimaryNEERay = packRGBE(pow(unpackRGBE(PrimaryNEERay), 2.2f) + pow(illumination, rcp(2.2f))).
+ * visibility (nullable): (1,1,1,1) not occluded, (0,0,0,0) occluded; rays with t == 0 are left unwritten.
+ * Flags as tt_trace_shadow_ex (TT_TRACE_STATS is accepted and reports nothing); TT_SHADOW_VISIBILITY_CHECK is
+ * TT_ERR_INVALID_ARG. Every output pointer may be NULL. TT_ERR_NO_SCENE without a terrain set.
+ * The reference's kernel_shadow with TerrainExists == true (:328, :459) only zeroes the t of occluded rays
+ * and accumulates nothing; a host gets that form by calling tt_trace_shadow_ex with NULL global_colors,
+ * nee_pos and cache_buffer and then this function on the same rays (tt_trace_shadow_ex itself is
+ * unchanged). */
+tt_status tt_trace_shadow_heightmap(tt_ctx* ctx, const tt_shadow_params* p, tt_shadow_ray* shadow_rays,
+                                    float* visibility, tt_col_data* global_colors, float* nee_pos,
+                                    tt_cache_data* cache_buffer);
+tt_status tt_trace_shadow_heightmap_indirect(tt_ctx* ctx, const tt_shadow_params* p, const uint32_t* n_rays_dev,
+                                             tt_shadow_ray* shadow_rays, float* visibility,
+                                             tt_col_data* global_colors, float* nee_pos,
+                                             tt_cache_data* cache_buffer);
+
 /* ------------------------------------------------- attribute resolve */
 /* Parity aid for "normals within 1e-5": per hit, the interpolated shading normal
  * (GetTriangleNormal, CommonData.cginc:904-911) with Inverse = transpose of W2L's
  * 3x3 (RayTracingShader.compute:99-118) and the geometric normal. Out: float[6] per
- * ray (shading xyz, geometric xyz); misses write zeros. */
+ * ray (shading xyz, geometric xyz); misses write zeros. On a context with terrains a hit with
+ * mesh_id == TT_TERRAIN_MESH_ID and triangle_id < the terrain count writes GetHeightmapNormal
+ * (CommonData.cginc:922-938) at origin + direction * t to both slots (RayTracingShader.compute:109-111);
+ * without a terrain set such a record writes zeros, as ever. */
 tt_status tt_resolve_normals(tt_ctx* ctx, const tt_trace_params* p,
                              const tt_ray_data* global_rays, float* normals6);
 
@@ -674,7 +763,9 @@ tt_status tt_generate_primary(tt_ctx* ctx, const tt_camera* cam, tt_ray_data* gl
  * source order (a stable single-pass scan: 4096-ray tiles, block ballot / LDS prefix, decoupled
  * look-back over the preceding tiles' counts; the reference's InterlockedAdd order,
  * RayTracingShader.compute:500, is whatever its atomics serialise to); *n_next receives their
- * count. */
+ * count. On a context with terrains a hit with mesh_id == TT_TERRAIN_MESH_ID terminates its path (bouncing
+ * off terrain needs the terrain normal inside kernel_shade's subset: not built yet); without a terrain set
+ * nothing changes. */
 tt_status tt_enqueue_diffuse_bounce(tt_ctx* ctx, const tt_trace_params* p, tt_ray_data* global_rays,
                                     int32_t frames_accumulated, int32_t max_bounce, uint32_t* n_next);
 /* The same enqueue with device-resident counts: reads the traced count from n_rays_dev (nullable:

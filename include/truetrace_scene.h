@@ -132,6 +132,30 @@ tt_status tt_bvh2_build(const float* aabbs_maxmin, uint32_t n, int32_t* final_in
 /* .NET Framework IntrospectiveSort with a float-key Comparison (BVH2Builder.cs:137-147). */
 void tt_dotnet_sort_by_key(int32_t* items, uint32_t n, const float* keys);
 
+/* Terrains: scalar restatements of kernel_heightmap, kernel_shadow_heightmap's occlusion test and
+ * GetHeightmapNormal (IntersectionKernels.compute:508-710, CommonData.cginc:922-938), the host reference of
+ * tt_trace_heightmap / tt_trace_shadow_heightmap / tt_resolve_normals (host/tt_terrain.cpp; numerics as
+ * pinned in truetrace_hip.h). heightmap: w * h binary16 texels. */
+/* In place on rays (the bounce half p selects) and primary_info (nullable), as tt_trace_heightmap with host
+ * pointers. stats (nullable): rays, hits, node_visits (samples), reps_exhausted (marches at the step bound). */
+tt_status tt_terrain_trace_host(const tt_terrain* terrains, uint32_t n, const uint16_t* heightmap, uint32_t w,
+                                uint32_t h, const tt_trace_params* p, tt_ray_data* rays, uint32_t* primary_info,
+                                tt_stats* stats);
+/* The same, plus one word per ray in detail (nullable): bit 0 the record was rewritten, bit 1 a bisection ran,
+ * bit 2 a march ended at the step bound, bits 8-15 the terrains (index < 8) whose box test passed, bits
+ * 16-23 the terrains (index < 8) that were hit. */
+tt_status tt_terrain_trace_detail_host(const tt_terrain* terrains, uint32_t n, const uint16_t* heightmap, uint32_t w,
+                                       uint32_t h, const tt_trace_params* p, tt_ray_data* rays,
+                                       uint32_t* primary_info, tt_stats* stats, uint32_t* detail);
+/* occluded_out[i] = 1 when a terrain occludes shadow ray i (rays with t == 0 are not marched: 0). stats
+ * (nullable): rays (marched), hits (occluded), node_visits, reps_exhausted. */
+tt_status tt_terrain_occluded_host(const tt_terrain* terrains, uint32_t n, const uint16_t* heightmap, uint32_t w,
+                                   uint32_t h, const tt_shadow_ray* shadow_rays, uint32_t n_rays,
+                                   uint8_t* occluded_out, tt_stats* stats);
+/* GetHeightmapNormal(position, terrain_id). */
+tt_status tt_terrain_normal_host(const tt_terrain* terrains, uint32_t n, const uint16_t* heightmap, uint32_t w,
+                                 uint32_t h, const float* position3, uint32_t terrain_id, float* normal3);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,11 +41,15 @@ hipError_t tt_launch_bounce(tt_ray_data* rays, uint32_t src_off, uint32_t dst_of
                             int32_t cur_bounce, int32_t frames, int32_t max_bounce, const tt_cuda_triangle* tris,
                             const tt_mesh_data* md, uint32_t* counter, hipStream_t st, const uint32_t* n_dev,
                             uint32_t* n_next_dev, uint32_t* ctl_next, uint32_t ctl_next_words,
-                            uint32_t frame_pixels);
+                            uint32_t frame_pixels, uint32_t terrains);
 uint32_t tt_bounce_tiles(uint32_t n);
 hipError_t tt_launch_resolve(const tt_ray_data* rays, uint32_t ray_offset, uint32_t n, float far_plane,
                              const tt_cuda_triangle* tris, uint32_t n_tris, const tt_mesh_data* md, uint32_t n_mesh,
-                             float* out, hipStream_t st);
+                             float* out, hipStream_t st, const tt_terrain* terrains, uint32_t n_terrains,
+                             const uint16_t* hmap, uint32_t hmap_w, uint32_t hmap_h);
+hipError_t tt_launch_terrain(const TerrainArgs* a, int shadow, int stats, int grid_form, uint32_t grid, hipStream_t st);
+hipError_t tt_launch_terrain_shadow_outputs(const ShadowArgs* a, hipStream_t st);
+void tt_terrain_occupancy_table(int* out3);
 hipError_t tt_launch_rcp_selftest(unsigned long long* d_bad, hipStream_t st);
 
 namespace {
@@ -155,6 +159,13 @@ struct tt_ctx {
     uint32_t tex_w = 0, tex_h = 0;
     DevBuf<uint8_t> atlas;      // _AlphaAtlas (R8)
     uint32_t atlas_w = 0, atlas_h = 0;
+    // Terrains + the Heightmap atlas (tt_scene_upload_terrains): part of the scene like the atlases
+    DevBuf<tt_terrain> terrains;  // device copy (tt_resolve_normals indexes it per hit)
+    std::vector<tt_terrain> terrains_host;  // each march launch carries its terrain in the kernel arguments
+    DevBuf<uint16_t> hmap;        // binary16 texels
+    uint32_t hmap_w = 0, hmap_h = 0;
+    uint32_t terrain_grid_of[3] = {};  // resident persistent grids: closest hit, with stats, shadow (0: not sized yet)
+    DevBuf<unsigned char> st_touched;  // TT_TRACE_STATS: per ray, its record was rewritten by this call
     // TT_ROOT_LEAF: node 0 as the device holds it is known on the host (upload, node updates); a device
     // refit of the TLAS rewrites it without a read-back, so the fast root step is off until the next update
     bool root_known = false;
@@ -1012,6 +1023,9 @@ tt_status tt_ctx_destroy(tt_ctx* c) {
     c->leaf.release();
     c->atlas.release();
     c->tex.release();
+    c->terrains.release();
+    c->hmap.release();
+    c->st_touched.release();
     tt_refit_free(c->refit);
     for (auto& kv : c->blas_refit) {
         tt_refit_free(kv.second.dev);
@@ -1300,6 +1314,11 @@ tt_status share_begin(tt_ctx* dst, tt_ctx* src) {
     dst->mat_glass.borrow(src->mat_glass);
     dst->tex.borrow(src->tex);
     dst->atlas.borrow(src->atlas);
+    dst->terrains.borrow(src->terrains);
+    dst->hmap.borrow(src->hmap);
+    dst->terrains_host = src->terrains_host;
+    dst->hmap_w = src->hmap_w;
+    dst->hmap_h = src->hmap_h;
     dst->tex_w = src->tex_w;
     dst->tex_h = src->tex_h;
     dst->atlas_w = src->atlas_w;
@@ -1484,6 +1503,9 @@ tt_status tt_ctx_share_blas(tt_ctx* dst, tt_ctx* src, uint32_t n_tlas_nodes) {
         dst->mat_glass.release();
         dst->tex.release();
         dst->atlas.release();
+        dst->terrains.release();
+        dst->hmap.release();
+        dst->terrains_host.clear();
         dst->tlas.release();
         dst->mesh_raw.release();
         dst->mesh.release();
@@ -1863,7 +1885,8 @@ tt_status tt_scene_update_meshdata(tt_ctx* c, uint32_t first, uint32_t count, co
 tt_status tt_scene_bytes(const tt_ctx* c, uint64_t* bytes) {
     if (!c || !bytes) return TT_ERR_INVALID_ARG;
     *bytes = c->nodes.n * sizeof(tt_cwbvh_node) + c->nodes_k.n + c->tris_raw.n * sizeof(tt_cuda_triangle) + c->tris.n * sizeof(TriPos) +
-             c->tlas.n * 4 + c->mesh_raw.n * sizeof(tt_mesh_data) + c->mesh.n * sizeof(MeshGpu) + c->mat_tag.n * 4;
+             c->tlas.n * 4 + c->mesh_raw.n * sizeof(tt_mesh_data) + c->mesh.n * sizeof(MeshGpu) + c->mat_tag.n * 4 +
+             c->hmap.n * sizeof(uint16_t) + c->terrains.n * sizeof(tt_terrain);
     return TT_OK;
 }
 
@@ -2369,7 +2392,8 @@ tt_status tt_resolve_normals(tt_ctx* c, const tt_trace_params* p, const tt_ray_d
     SceneRead sr(c);
     TT_HIP(c, sr.err);
     TT_HIP(c, tt_launch_resolve(d_rays, off, p->n_rays, p->far_plane, c->tris_raw.p, (uint32_t)c->tris_raw.n,
-                                c->mesh_raw.p, (uint32_t)c->mesh_raw.n, d_out, c->stream));
+                                c->mesh_raw.p, (uint32_t)c->mesh_raw.n, d_out, c->stream, c->terrains.p,
+                                (uint32_t)c->terrains_host.size(), c->hmap.p, c->hmap_w, c->hmap_h));
     sr.end();
     if (!dev) TT_HIP(c, hipMemcpyAsync(normals6, d_out, sizeof(float) * 6 * p->n_rays, hipMemcpyDeviceToHost, c->stream));
     TT_HIP(c, hipStreamSynchronize(c->stream));
@@ -2454,7 +2478,7 @@ static tt_status enqueue_call(tt_ctx* c, const tt_trace_params* p, const uint32_
     TT_HIP(c, ring_open(c, slot));
     TT_HIP(c, tt_launch_bounce(d, src, dst, p->n_rays, p->far_plane, p->bounce, frames, max_bounce, c->tris_raw.p,
                                c->mesh_raw.p, ctl_cur, c->stream, n_dev, n_next_dev, ctl_next, c->counter_words,
-                               c->frame_pixels));
+                               c->frame_pixels, c->terrains_host.empty() ? 0u : 1u));
     c->counter_cur ^= 1u;
     TT_HIP(c, ring_close(c, slot));
     sr.end();
@@ -2485,6 +2509,346 @@ tt_status tt_enqueue_diffuse_bounce_indirect(tt_ctx* c, const tt_trace_params* p
                                              uint32_t* n_next_dev) {
     if (!n_next_dev) return c ? fail(c, TT_ERR_INVALID_ARG, "null device survivor count") : TT_ERR_INVALID_ARG;
     return enqueue_call(c, p, n_rays_dev, rays, frames, max_bounce, nullptr, n_next_dev);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ terrains (tt_terrain.hip)
+namespace {
+
+// tt_terrain_validate's check; why receives the first violation
+tt_status check_terrains(const tt_terrain* t, uint32_t n, const uint16_t* hm, uint32_t w, uint32_t h, std::string& why) {
+    char buf[160];
+    if (n == 0) return TT_OK;
+    if (!t) {
+        why = "null terrain array";
+        return TT_ERR_INVALID_ARG;
+    }
+    if (!hm || w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) {
+        why = "empty or oversized heightmap atlas";
+        return TT_ERR_INVALID_ARG;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        const float* f = reinterpret_cast<const float*>(t + i);
+        static const char* names[14] = {"PositionOffset.x", "PositionOffset.y", "PositionOffset.z", "HeightScale",
+                                        "TerrainDim.x", "TerrainDim.y", "AlphaMap.x", "AlphaMap.y", "AlphaMap.z",
+                                        "AlphaMap.w", "HeightMap.x", "HeightMap.y", "HeightMap.z", "HeightMap.w"};
+        for (int k = 0; k < 14; k++)
+            if (!std::isfinite(f[k])) {
+                std::snprintf(buf, sizeof(buf), "terrain %u: %s is not finite", i, names[k]);
+                why = buf;
+                return TT_ERR_INVALID_ARG;
+            }
+        for (int k = 0; k < 4; k++)
+            if (!(t[i].HeightMap[k] >= 0.0f && t[i].HeightMap[k] <= 1.0f)) {
+                std::snprintf(buf, sizeof(buf), "terrain %u: HeightMap rectangle component %d = %g lies outside [0, 1]", i,
+                              k, (double)t[i].HeightMap[k]);
+                why = buf;
+                return TT_ERR_INVALID_ARG;
+            }
+    }
+    return TT_OK;
+}
+
+// The march kernels' form. The one-thread-per-ray grid kernels are the product: on the measured workloads
+// (profiles/r08/terrain/bench.json) they beat the persistent refill kernels, which TT_TERRAIN_FORM=persistent
+// (read once per process) selects for A/B measurement. Results are identical in both forms.
+bool terrain_grid_form() {
+    static const bool grid = [] {
+        const char* e = std::getenv("TT_TERRAIN_FORM");
+        return !(e && std::strcmp(e, "persistent") == 0);
+    }();
+    return grid;
+}
+
+// resident persistent grid of the march kernels, sized on first use; kind: 0 closest hit, 1 with stats, 2 shadow
+uint32_t terrain_grid(tt_ctx* c, int kind, uint32_t n_rays) {
+    if (terrain_grid_form()) return 0u;  // (the grid form sizes itself by the ray count)
+    if (!c->terrain_grid_of[0]) {
+        int occ[3];
+        tt_terrain_occupancy_table(occ);
+        for (int k = 0; k < 3; k++) c->terrain_grid_of[k] = (uint32_t)(c->num_cus * std::max(1, std::min(occ[k], 32)));
+    }
+    return std::max(1u, std::min(c->terrain_grid_of[kind], (n_rays + 63u) / 64u));
+}
+
+// the scheduler tickets (and, first = true, the stats) of the launch's control block
+hipError_t reset_terrain_control(tt_ctx* c, bool first) {
+    if (!first && terrain_grid_form()) return hipSuccess;  // (no tickets; the stats accumulate over the terrains)
+    c->ctl_zero[0] = c->ctl_zero[1] = false;  // the march kernels zero nothing for later trace launches
+    return hipMemsetAsync(c->ctl + c->ctl_cur, 0, first ? sizeof(TraceControl) : offsetof(TraceControl, stats), c->stream);
+}
+
+void fill_terrain_args(const tt_ctx* c, uint32_t i, TerrainArgs& a) {
+    a.T = c->terrains_host[i];
+    a.terrain_index = i;
+    a.hmap = c->hmap.p;
+    a.map_w = c->hmap_w;
+    a.map_h = c->hmap_h;
+    a.ctl = c->ctl + c->ctl_cur;
+}
+
+tt_status heightmap_call(tt_ctx* c, const tt_trace_params* p, const uint32_t* n_dev, tt_ray_data* rays, uint32_t* info,
+                         tt_stats* stats) {
+    if (!c) return TT_ERR_INVALID_ARG;
+    TT_REFUSE_DEAD_STREAM(c);
+    if (c->terrains_host.empty()) return fail(c, TT_ERR_NO_SCENE, "no terrain set uploaded (tt_scene_upload_terrains)");
+    if (!p || !rays) return fail(c, TT_ERR_INVALID_ARG, "null params or rays");
+    if (p->screen_width == 0 || p->screen_height == 0) return fail(c, TT_ERR_INVALID_ARG, "zero screen size");
+    if (p->bounce < 0) return fail(c, TT_ERR_INVALID_ARG, "negative bounce");
+    const uint64_t wh = (uint64_t)p->screen_width * p->screen_height;
+    if (wh > 0x7fffffffull) return fail(c, TT_ERR_INVALID_ARG, "screen too large");
+    const uint32_t off = (p->bounce % 2 == 1) ? (uint32_t)wh : 0u;
+    if ((uint64_t)off + p->n_rays > 0xffffffffull) return fail(c, TT_ERR_INVALID_ARG, "ray range overflows");
+    const bool dev = (p->flags & TT_TRACE_DEVICE_PTRS) != 0;
+    const bool async = dev && ((p->flags & TT_TRACE_ASYNC) || n_dev);
+    const bool want_stats = (p->flags & TT_TRACE_STATS) != 0;
+    if (n_dev) {
+        if (!dev) return fail(c, TT_ERR_INVALID_ARG, "a device-resident ray count needs TT_TRACE_DEVICE_PTRS");
+        if (want_stats) return fail(c, TT_ERR_INVALID_ARG, "TT_TRACE_STATS needs a host ray count");
+        if (!is_device_ptr(n_dev)) return fail(c, TT_ERR_INVALID_ARG, "the ray count pointer is not device memory");
+    }
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (p->n_rays == 0) return TT_OK;
+    if (reinterpret_cast<uintptr_t>(rays) % 16 || (info && reinterpret_cast<uintptr_t>(info) % 16))
+        return fail(c, TT_ERR_INVALID_ARG, "GlobalRays / _PrimaryTriangleInfo must be 16-byte aligned");
+    TT_HIP(c, hipSetDevice(c->device));
+    tt_ray_data* d_rays = rays;
+    uint32_t* d_info = info;
+    if (dev) {
+        if (!is_device_ptr(rays)) return fail(c, TT_ERR_INVALID_ARG, "TT_TRACE_DEVICE_PTRS set but rays is not device memory");
+    } else {
+        const size_t ray_end = (size_t)off + p->n_rays;
+        if (c->st_rays.n < ray_end) TT_HIP(c, c->st_rays.alloc(ray_end));
+        d_rays = c->st_rays.p;
+        TT_HIP(c, hipMemcpyAsync(d_rays + off, rays + off, sizeof(tt_ray_data) * p->n_rays, hipMemcpyHostToDevice, c->stream));
+        if (info) {
+            if (c->st_info.n < wh * 4) TT_HIP(c, c->st_info.alloc(wh * 4));
+            d_info = c->st_info.p;
+            TT_HIP(c, hipMemcpyAsync(d_info, info, sizeof(uint32_t) * 4 * wh, hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    if (want_stats) {
+        if (c->st_touched.n < p->n_rays) TT_HIP(c, c->st_touched.alloc(p->n_rays));
+        TT_HIP(c, hipMemsetAsync(c->st_touched.p, 0, p->n_rays, c->stream));
+    }
+    TerrainArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.rays = d_rays;
+    a.info = d_info;
+    a.touched = want_stats ? c->st_touched.p : nullptr;
+    a.n_rays = p->n_rays;
+    a.n_rays_dev = n_dev;
+    a.ray_offset = off;
+    a.n_pixels = (uint32_t)wh;
+    a.bounce = p->bounce;
+    a.flags = p->flags;
+    const uint32_t grid = terrain_grid(c, want_stats ? 1 : 0, p->n_rays);
+    const uint32_t slot = c->ring_n % TT_RING;
+    const bool ring = c->timing || !async;  // (a synchronous call reports its kernels' time)
+    TT_HIP(c, reset_terrain_control(c, true));
+    if (ring) TT_HIP(c, hipEventRecord(c->ring0[slot], c->stream));
+    for (uint32_t i = 0; i < (uint32_t)c->terrains_host.size(); i++) {  // in order: terrain i + 1 sees i's shortened t
+        if (i) TT_HIP(c, reset_terrain_control(c, false));
+        fill_terrain_args(c, i, a);
+        TT_HIP(c, tt_launch_terrain(&a, 0, want_stats ? 1 : 0, terrain_grid_form() ? 1 : 0, grid, c->stream));
+    }
+    note_stream_launch(c->stream);
+    if (ring) {
+        TT_HIP(c, hipEventRecord(c->ring1[slot], c->stream));
+        c->ring_n++;
+        c->ev0 = c->ring0[slot];
+        c->ev1 = c->ring1[slot];
+    }
+    if (async) return TT_OK;
+    TraceControl ctl;
+    TT_HIP(c, hipMemcpyAsync(&ctl, c->ctl + c->ctl_cur, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+    if (!dev) {
+        TT_HIP(c, hipMemcpyAsync(rays + off, d_rays + off, sizeof(tt_ray_data) * p->n_rays, hipMemcpyDeviceToHost, c->stream));
+        if (info) TT_HIP(c, hipMemcpyAsync(info, d_info, sizeof(uint32_t) * 4 * wh, hipMemcpyDeviceToHost, c->stream));
+    }
+    TT_HIP(c, hipStreamSynchronize(c->stream));
+    if (stats) {
+        TT_HIP(c, hipEventElapsedTime(&stats->kernel_ms, c->ev0, c->ev1));
+        if (want_stats) {
+            stats->rays = p->n_rays;
+            stats->node_visits = ctl.stats[1];
+            stats->hits = ctl.stats[4];
+            stats->reps_exhausted = ctl.stats[5];
+        }
+    }
+    return TT_OK;
+}
+
+tt_status shadow_heightmap_call(tt_ctx* c, const tt_shadow_params* p, const uint32_t* n_dev, tt_shadow_ray* rays,
+                                float* visibility, tt_col_data* colors, float* nee_pos, tt_cache_data* cache) {
+    if (!c) return TT_ERR_INVALID_ARG;
+    TT_REFUSE_DEAD_STREAM(c);
+    if (c->terrains_host.empty()) return fail(c, TT_ERR_NO_SCENE, "no terrain set uploaded (tt_scene_upload_terrains)");
+    if (!p || !rays) return fail(c, TT_ERR_INVALID_ARG, "null params or shadow rays");
+    if (p->screen_width == 0 || p->screen_height == 0) return fail(c, TT_ERR_INVALID_ARG, "zero screen size");
+    if (p->bounce < 0) return fail(c, TT_ERR_INVALID_ARG, "negative bounce");
+    if (p->flags & TT_SHADOW_VISIBILITY_CHECK)
+        return fail(c, TT_ERR_INVALID_ARG, "TT_SHADOW_VISIBILITY_CHECK has no heightmap form (VisabilityCheckCompute never marches terrains)");
+    const uint64_t wh = (uint64_t)p->screen_width * p->screen_height;
+    if (wh > 0x7fffffffull) return fail(c, TT_ERR_INVALID_ARG, "screen too large");
+    const bool dev = (p->flags & TT_TRACE_DEVICE_PTRS) != 0;
+    const bool async = dev && ((p->flags & TT_TRACE_ASYNC) || n_dev);
+    if (n_dev) {
+        if (!dev) return fail(c, TT_ERR_INVALID_ARG, "a device-resident ray count needs TT_TRACE_DEVICE_PTRS");
+        if (!is_device_ptr(n_dev)) return fail(c, TT_ERR_INVALID_ARG, "the ray count pointer is not device memory");
+    }
+    if (p->n_rays == 0) return TT_OK;
+    if (reinterpret_cast<uintptr_t>(rays) % 16 || (visibility && reinterpret_cast<uintptr_t>(visibility) % 16) ||
+        (nee_pos && reinterpret_cast<uintptr_t>(nee_pos) % 16))
+        return fail(c, TT_ERR_INVALID_ARG, "shadow rays / visibility / NEEPosA must be 16-byte aligned");
+    TT_HIP(c, hipSetDevice(c->device));
+    tt_shadow_ray* d_rays = rays;
+    float4* d_vis = reinterpret_cast<float4*>(visibility);
+    tt_col_data* d_col = colors;
+    float4* d_nee = reinterpret_cast<float4*>(nee_pos);
+    tt_cache_data* d_cache = cache;
+    if (dev) {
+        if (!is_device_ptr(rays)) return fail(c, TT_ERR_INVALID_ARG, "TT_TRACE_DEVICE_PTRS set but rays is not device memory");
+    } else {
+        if (cache) {
+            if (c->st_cache.n < wh) TT_HIP(c, c->st_cache.alloc(wh));
+            d_cache = c->st_cache.p;
+            TT_HIP(c, hipMemcpyAsync(d_cache, cache, sizeof(tt_cache_data) * wh, hipMemcpyHostToDevice, c->stream));
+        }
+        if (c->st_shadow.n < p->n_rays) TT_HIP(c, c->st_shadow.alloc(p->n_rays));
+        d_rays = c->st_shadow.p;
+        TT_HIP(c, hipMemcpyAsync(d_rays, rays, sizeof(tt_shadow_ray) * p->n_rays, hipMemcpyHostToDevice, c->stream));
+        if (colors) {
+            if (c->st_colors.n < wh) TT_HIP(c, c->st_colors.alloc(wh));
+            d_col = c->st_colors.p;
+            TT_HIP(c, hipMemcpyAsync(d_col, colors, sizeof(tt_col_data) * wh, hipMemcpyHostToDevice, c->stream));
+        }
+        if (nee_pos) {
+            if (c->st_nee.n < wh) TT_HIP(c, c->st_nee.alloc(wh));
+            d_nee = c->st_nee.p;
+            TT_HIP(c, hipMemcpyAsync(d_nee, nee_pos, sizeof(float4) * wh, hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    // the per-ray visibility record carries "not occluded so far" from one terrain's launch to the next and to
+    // the output pass: the caller's array, or the context's scratch (a host array is staged: rays with t == 0
+    // keep the caller's values)
+    if (!dev || !d_vis) {
+        if (c->st_vis.n < p->n_rays) TT_HIP(c, c->st_vis.alloc(p->n_rays));
+        d_vis = c->st_vis.p;
+        if (visibility)
+            TT_HIP(c, hipMemcpyAsync(d_vis, visibility, sizeof(float4) * p->n_rays, hipMemcpyHostToDevice, c->stream));
+    }
+    TerrainArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.srays = d_rays;
+    a.vis = d_vis;
+    a.n_rays = p->n_rays;
+    a.n_rays_dev = n_dev;
+    a.n_pixels = (uint32_t)wh;
+    a.bounce = p->bounce;
+    a.flags = p->flags;
+    const uint32_t grid = terrain_grid(c, 2, p->n_rays);
+    const uint32_t slot = c->ring_n % TT_RING;
+    const bool ring = c->timing || !async;
+    TT_HIP(c, reset_terrain_control(c, true));
+    if (ring) TT_HIP(c, hipEventRecord(c->ring0[slot], c->stream));
+    for (uint32_t i = 0; i < (uint32_t)c->terrains_host.size(); i++) {
+        if (i) TT_HIP(c, reset_terrain_control(c, false));
+        fill_terrain_args(c, i, a);
+        TT_HIP(c, tt_launch_terrain(&a, 1, 0, terrain_grid_form() ? 1 : 0, grid, c->stream));
+    }
+    ShadowArgs o;
+    std::memset(&o, 0, sizeof(o));
+    o.rays = d_rays;
+    o.visibility = d_vis;
+    o.colors = d_col;
+    o.nee_pos = d_nee;
+    o.cache = d_cache;
+    o.n_rays = p->n_rays;
+    o.n_rays_dev = n_dev;
+    o.width = p->screen_width;
+    o.height = p->screen_height;
+    o.bounce = p->bounce;
+    o.flags = p->flags;
+    if (d_col || d_nee || d_cache) TT_HIP(c, tt_launch_terrain_shadow_outputs(&o, c->stream));
+    note_stream_launch(c->stream);
+    if (ring) {
+        TT_HIP(c, hipEventRecord(c->ring1[slot], c->stream));
+        c->ring_n++;
+        c->ev0 = c->ring0[slot];
+        c->ev1 = c->ring1[slot];
+    }
+    if (async) return TT_OK;
+    if (!dev) {
+        if (visibility)
+            TT_HIP(c, hipMemcpyAsync(visibility, d_vis, sizeof(float4) * p->n_rays, hipMemcpyDeviceToHost, c->stream));
+        if (colors) TT_HIP(c, hipMemcpyAsync(colors, d_col, sizeof(tt_col_data) * wh, hipMemcpyDeviceToHost, c->stream));
+        if (nee_pos) TT_HIP(c, hipMemcpyAsync(nee_pos, d_nee, sizeof(float4) * wh, hipMemcpyDeviceToHost, c->stream));
+        if (cache) TT_HIP(c, hipMemcpyAsync(cache, d_cache, sizeof(tt_cache_data) * wh, hipMemcpyDeviceToHost, c->stream));
+    }
+    TT_HIP(c, hipStreamSynchronize(c->stream));
+    return TT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+tt_status tt_terrain_validate(const tt_terrain* terrains, uint32_t n, const uint16_t* heightmap_half, uint32_t width,
+                              uint32_t height, char* why, uint32_t why_len) {
+    std::string w;
+    const tt_status st = check_terrains(terrains, n, heightmap_half, width, height, w);
+    if (why && why_len) std::snprintf(why, why_len, "%s", w.c_str());
+    return st;
+}
+
+tt_status tt_scene_upload_terrains(tt_ctx* c, const tt_terrain* terrains, uint32_t n, const uint16_t* heightmap_half,
+                                   uint32_t width, uint32_t height) {
+    if (!c) return TT_ERR_INVALID_ARG;
+    TT_REFUSE_DEAD_STREAM(c);
+    TT_REFUSE_BORROWER(c);
+    TT_REFUSE_LENDER(c);
+    std::string why;
+    const tt_status vs = check_terrains(terrains, n, heightmap_half, width, height, why);
+    if (vs != TT_OK) return fail(c, vs, "tt_scene_upload_terrains: %s", why.c_str());
+    TT_HIP(c, hipSetDevice(c->device));
+    TT_HIP(c, hipStreamSynchronize(c->stream));  // no launch still reads the previous set
+    c->terrains_host.clear();
+    c->terrains.release();
+    c->hmap.release();
+    c->hmap_w = c->hmap_h = 0;
+    if (n == 0) return TT_OK;
+    TT_HIP(c, c->terrains.alloc(n));
+    TT_HIP(c, c->hmap.alloc((size_t)width * height));
+    TT_HIP(c, hipMemcpy(c->terrains.p, terrains, sizeof(tt_terrain) * n, hipMemcpyHostToDevice));
+    TT_HIP(c, hipMemcpy(c->hmap.p, heightmap_half, sizeof(uint16_t) * (size_t)width * height, hipMemcpyHostToDevice));
+    c->hmap_w = width;
+    c->hmap_h = height;
+    c->terrains_host.assign(terrains, terrains + n);
+    return TT_OK;
+}
+
+tt_status tt_trace_heightmap(tt_ctx* c, const tt_trace_params* p, tt_ray_data* rays, uint32_t* info, tt_stats* stats) {
+    return heightmap_call(c, p, nullptr, rays, info, stats);
+}
+
+tt_status tt_trace_heightmap_indirect(tt_ctx* c, const tt_trace_params* p, const uint32_t* n_rays_dev, tt_ray_data* rays,
+                                      uint32_t* info) {
+    if (!n_rays_dev) return c ? fail(c, TT_ERR_INVALID_ARG, "null device ray count") : TT_ERR_INVALID_ARG;
+    return heightmap_call(c, p, n_rays_dev, rays, info, nullptr);
+}
+
+tt_status tt_trace_shadow_heightmap(tt_ctx* c, const tt_shadow_params* p, tt_shadow_ray* rays, float* visibility,
+                                    tt_col_data* colors, float* nee_pos, tt_cache_data* cache) {
+    return shadow_heightmap_call(c, p, nullptr, rays, visibility, colors, nee_pos, cache);
+}
+
+tt_status tt_trace_shadow_heightmap_indirect(tt_ctx* c, const tt_shadow_params* p, const uint32_t* n_rays_dev,
+                                             tt_shadow_ray* rays, float* visibility, tt_col_data* colors, float* nee_pos,
+                                             tt_cache_data* cache) {
+    if (!n_rays_dev) return c ? fail(c, TT_ERR_INVALID_ARG, "null device ray count") : TT_ERR_INVALID_ARG;
+    return shadow_heightmap_call(c, p, n_rays_dev, rays, visibility, colors, nee_pos, cache);
 }
 
 }  // extern "C"

@@ -257,6 +257,28 @@ struct ShadowArgs {
     uint32_t tlas_base;          // as TraceArgs::tlas_base
 };
 
+// Heightmap march launch (tt_terrain.hip: kernel_heightmap / kernel_shadow_heightmap replacements). One
+// launch marches ONE terrain, so its TerrainData travels in the kernel arguments (wave-uniform scalars); the
+// API issues one launch per terrain in order, each seeing the records the previous one shortened.
+struct TerrainArgs {
+    tt_terrain T;                // this launch's terrain
+    uint32_t terrain_index;      // triangle_id of its hit records
+    const uint16_t* hmap;        // Heightmap atlas, binary16 texels
+    uint32_t map_w, map_h;
+    tt_ray_data* rays;           // closest hit: GlobalRays (records rewritten in place)
+    uint32_t* info;              // closest hit: _PrimaryTriangleInfo, nullable
+    unsigned char* touched;      // closest hit, STATS: per ray of the launch, 1 once its record was rewritten
+    const tt_shadow_ray* srays;  // shadow: ShadowRaysBuffer (read only)
+    float4* vis;                 // shadow: per ray, (1,1,1,1) not occluded so far / (0,0,0,0) occluded
+    TraceControl* ctl;
+    uint32_t n_rays;             // rays of the launch; with n_rays_dev: the capacity
+    const uint32_t* n_rays_dev;  // nullable: device-resident count
+    uint32_t ray_offset;         // closest hit: W*H on odd bounces
+    uint32_t n_pixels;           // W*H
+    int32_t bounce;
+    uint32_t flags;              // TT_TRACE_*
+};
+
 // The launch's ray count: the host value, or the device-resident count clamped to it (a wave-uniform
 // load of a word an earlier operation on the stream wrote).
 template <class Args>

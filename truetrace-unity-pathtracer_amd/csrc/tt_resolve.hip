@@ -3,7 +3,7 @@
 // (RayTracingShader.compute:111-118), both through Inverse = transpose((float3x3)W2L).
 // Not part of the trace hot loop; it exists so "normals within 1e-5" is checkable at the
 // boundary. One ray per lane, HBM-bound (48 B ray + 88 B triangle + 64 B W2L in, 24 B out).
-#include "tt_device.h"
+#include "tt_terrain.h"
 
 namespace {
 
@@ -25,6 +25,23 @@ __device__ __forceinline__ float3 i_octahedral_32(uint32_t data) {
     return normalize3(nor);
 }
 
+// GetHeightRaw / GetHeightmapNormal — CommonData.cginc:922-938
+__device__ __forceinline__ float height_raw(const tt_ter::HeightView& M, const tt_terrain& T, float x, float z) {
+    x = x - T.PositionOffset[0];
+    z = z - T.PositionOffset[2];
+    const float dx = T.TerrainDim[0], dz = T.TerrainDim[1];
+    const float u = tt_ter::min_nn(x / dx, dx / dx), v = tt_ter::min_nn(z / dz, dz / dz);
+    return tt_ter::height(M, T, u, v) * (T.HeightScale * 2.0f);
+}
+__device__ __forceinline__ float3 heightmap_normal(const tt_ter::HeightView& M, const tt_terrain& T, float3 p) {
+    const float3 c = make_float3(p.x, height_raw(M, T, p.x, p.z), p.z);
+    const float3 ox = make_float3(p.x + 0.25f, height_raw(M, T, p.x + 0.25f, p.z + 0.0f), p.z);
+    const float3 oy = make_float3(p.x, height_raw(M, T, p.x + 0.0f, p.z + 0.25f), p.z + 0.25f);
+    const float3 a = normalize3(make_float3(ox.x - c.x, ox.y - c.y, ox.z - c.z));
+    const float3 b = normalize3(make_float3(oy.x - c.x, oy.y - c.y, oy.z - c.z));
+    return normalize3(make_float3(fma_(a.y, b.z, -(a.z * b.y)), fma_(a.z, b.x, -(a.x * b.z)), fma_(a.x, b.y, -(a.y * b.x))));
+}
+
 // mul(Inverse, x) with Inverse = transpose(W2L 3x3): row r = sum_c W2L(c, r) * x_c
 __device__ __forceinline__ float3 mul_inv(const float* W, float3 x) {
     auto M = [&](int r, int c) { return W[c * 4 + r]; };
@@ -36,7 +53,9 @@ __device__ __forceinline__ float3 mul_inv(const float* W, float3 x) {
 __global__ __launch_bounds__(256) void tt_resolve_kernel(const tt_ray_data* __restrict__ rays, uint32_t off, uint32_t n,
                                                          float far_plane, const tt_cuda_triangle* __restrict__ tris,
                                                          uint32_t n_tris, const tt_mesh_data* __restrict__ md,
-                                                         uint32_t n_mesh, float* __restrict__ out) {
+                                                         uint32_t n_mesh, float* __restrict__ out,
+                                                         const tt_terrain* __restrict__ terrains, uint32_t n_terrains,
+                                                         tt_ter::HeightView hmap) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const tt_ray_data* r = rays + off + i;
@@ -44,6 +63,16 @@ __global__ __launch_bounds__(256) void tt_resolve_kernel(const tt_ray_data* __re
     const uint4 h = reinterpret_cast<const uint4*>(r)[2];
     const float t = __uint_as_float(h.z);
     const int32_t mesh_id = (int32_t)h.x, tri = (int32_t)h.y;
+    // a terrain hit (RayTracingShader.compute:109-111): Geomnorm = USGNorm = GetHeightmapNormal(pos, triangle_id)
+    if (n_terrains != 0u && t < far_plane && h.x == TT_TERRAIN_MESH_ID && h.y < n_terrains) {
+        const float3 pos = make_float3(r->direction[0] * t + r->origin[0], r->direction[1] * t + r->origin[1],
+                                       r->direction[2] * t + r->origin[2]);
+        const float3 nn = heightmap_normal(hmap, terrains[h.y], pos);
+        o[0] = o[3] = nn.x;
+        o[1] = o[4] = nn.y;
+        o[2] = o[5] = nn.z;
+        return;
+    }
     if (!(t < far_plane) || tri < 0 || (uint32_t)tri >= n_tris || (uint32_t)mesh_id >= n_mesh) {
         for (int k = 0; k < 6; k++) o[k] = 0.0f;
         return;
@@ -80,9 +109,10 @@ __global__ __launch_bounds__(256) void tt_resolve_kernel(const tt_ray_data* __re
 
 hipError_t tt_launch_resolve(const tt_ray_data* rays, uint32_t ray_offset, uint32_t n, float far_plane,
                              const tt_cuda_triangle* tris, uint32_t n_tris, const tt_mesh_data* md, uint32_t n_mesh,
-                             float* out, hipStream_t st) {
+                             float* out, hipStream_t st, const tt_terrain* terrains, uint32_t n_terrains,
+                             const uint16_t* hmap, uint32_t hmap_w, uint32_t hmap_h) {
     const uint32_t grid = (n + 255u) / 256u;
     hipLaunchKernelGGL(tt_resolve_kernel, dim3(grid), dim3(256), 0, st, rays, ray_offset, n, far_plane, tris, n_tris, md,
-                       n_mesh, out);
+                       n_mesh, out, terrains, n_terrains, tt_ter::HeightView{hmap, hmap_w, hmap_h});
     return hipGetLastError();
 }

@@ -49,6 +49,8 @@ TT_TRACE_FORM_NONE, TT_TRACE_FORM_GENERIC, TT_TRACE_FORM_LEAF = 0, 1, 2
 TT_ROOT_GENERIC, TT_ROOT_ONE_LEAF, TT_ROOT_ONE_INSTANCE = 0, 1, 2
 TT_SHADOW_RADIANCE_CACHE = 1 << 7    # RadianceCache define (GlobalDefines.cginc:15) for tt_trace_shadow_ex
 TT_SHADOW_VISIBILITY_CHECK = 1 << 8  # VisabilityCheckCompute semantics (CommonData.cginc:710-819)
+TT_TERRAIN_MESH_ID = 9999999   # mesh_id of a terrain hit record (IntersectionKernels.compute:686)
+TT_TERRAIN_MAX_STEPS = 2000    # step bound of the heightmap march per terrain (:535, :653)
 TT_STACK_SIZE = 16
 TT_MAX_REPS = 1000
 
@@ -93,6 +95,10 @@ SHADOW_DTYPE = np.dtype([("origin", "<f4", 3), ("LuminanceIncomming", "<f4"), ("
                          ("illumination", "<f4", 3), ("PixelIndex", "<u4")])
 assert SHADOW_DTYPE.itemsize == 48
 # PropogatedCacheData (CommonData.cginc:1621-1627, PropDepth 4): the RadianceCache record per pixel
+# TerrainData, 60 B (CommonVars.cs:147-157, CommonData.cginc:280-287)
+TERRAIN_DTYPE = np.dtype([("PositionOffset", "<f4", 3), ("HeightScale", "<f4"), ("TerrainDim", "<f4", 2),
+                          ("AlphaMap", "<f4", 4), ("HeightMap", "<f4", 4), ("MatOffset", "<i4")])
+assert TERRAIN_DTYPE.itemsize == 60
 CACHE_DTYPE = np.dtype([("samples", "<u4", (4, 2)), ("throughput", "<u4"), ("pathLength", "<u4"),
                         ("CurrentIlluminance", "<u4"), ("Norm", "<u4")])
 assert CACHE_DTYPE.itemsize == 48 and CACHE_DTYPE.fields["CurrentIlluminance"][1] == 40
@@ -191,14 +197,17 @@ HIP_SYMBOLS = ["tt_abi_version", "tt_device_count", "tt_ctx_create", "tt_ctx_des
                "tt_trace_closest", "tt_sync", "tt_ctx_stream", "tt_resolve_normals", "tt_generate_primary",
                "tt_enqueue_diffuse_bounce", "tt_trace_closest_indirect", "tt_enqueue_diffuse_bounce_indirect",
                "tt_trace_shadow_ex_indirect", "tt_timing_reset", "tt_timing_read", "tt_scene_validate", "tt_trace_diagnostics",
-               "tt_selftest_rcp", "tt_trace_closest_hits", "tt_ctx_share_scene"]
+               "tt_selftest_rcp", "tt_trace_closest_hits", "tt_ctx_share_scene", "tt_scene_upload_terrains",
+               "tt_terrain_validate", "tt_trace_heightmap", "tt_trace_heightmap_indirect", "tt_trace_shadow_heightmap",
+               "tt_trace_shadow_heightmap_indirect"]
 SCENE_SYMBOLS = ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_blas_free", "tt_scene_assemble",
                  "tt_scene_build_get_info", "tt_scene_build_copy", "tt_scene_build_free", "tt_pack_octahedral",
                  "tt_bvh2_build", "tt_dotnet_sort_by_key", "tt_synth_cornell", "tt_synth_soup", "tt_synth_sponza",
                  "tt_synth_prop", "tt_synth_ground", "tt_synth_san_miguel", "tt_synth_mesh_view", "tt_synth_mesh_free",
                  "tt_synth_mesh_from_arrays", "tt_blas_copy_leaf_order", "tt_blas_prepare_aabbs", "tt_bvh2_presort",
                  "tt_blas_build_from_bvh2", "tt_blas_build_from_cwbvh", "tt_blas_prepare",
-                 "tt_blas_build_from_cwbvh_prepared", "tt_blas_prep_free"]
+                 "tt_blas_build_from_cwbvh_prepared", "tt_blas_prep_free", "tt_terrain_trace_host",
+                 "tt_terrain_trace_detail_host", "tt_terrain_occluded_host", "tt_terrain_normal_host"]
 
 
 def scene_lib():
@@ -246,6 +255,14 @@ def scene_lib():
         L.tt_synth_mesh_free.restype = None
         L.tt_synth_mesh_from_arrays.argtypes = [vp, u32, vp, u32, vp]
         L.tt_synth_mesh_from_arrays.restype = vp
+        L.tt_terrain_trace_host.argtypes = [vp, u32, vp, u32, u32, C.POINTER(TraceParams), vp, vp, C.POINTER(Stats)]
+        L.tt_terrain_trace_detail_host.argtypes = [vp, u32, vp, u32, u32, C.POINTER(TraceParams), vp, vp,
+                                                   C.POINTER(Stats), vp]
+        L.tt_terrain_occluded_host.argtypes = [vp, u32, vp, u32, u32, vp, u32, vp, C.POINTER(Stats)]
+        L.tt_terrain_normal_host.argtypes = [vp, u32, vp, u32, u32, vp, u32, vp]
+        for s in ["tt_terrain_trace_host", "tt_terrain_trace_detail_host", "tt_terrain_occluded_host",
+                  "tt_terrain_normal_host"]:
+            getattr(L, s).restype = i32
         for s in ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_scene_assemble", "tt_scene_build_get_info",
                   "tt_scene_build_copy", "tt_bvh2_build", "tt_synth_cornell", "tt_synth_soup", "tt_synth_sponza",
                   "tt_synth_prop", "tt_synth_ground", "tt_synth_san_miguel", "tt_synth_mesh_view"]:
@@ -299,6 +316,16 @@ def hip_lib():
         L.tt_scene_upload_alpha_atlas.argtypes = [vp, vp, u32, u32]
         L.tt_scene_upload_texture_atlas.argtypes = [vp, vp, u32, u32]
         L.tt_tlas_refit.argtypes = [vp, u32, vp, u32, u32]
+        if hasattr(L, "tt_scene_upload_terrains"):  # (absent from older variant libraries)
+            L.tt_scene_upload_terrains.argtypes = [vp, vp, u32, vp, u32, u32]
+            L.tt_terrain_validate.argtypes = [vp, u32, vp, u32, u32, C.c_char_p, u32]
+            L.tt_trace_heightmap.argtypes = [vp, C.POINTER(TraceParams), vp, vp, C.POINTER(Stats)]
+            L.tt_trace_heightmap_indirect.argtypes = [vp, C.POINTER(TraceParams), vp, vp, vp]
+            L.tt_trace_shadow_heightmap.argtypes = [vp, C.POINTER(ShadowParams), vp, vp, vp, vp, vp]
+            L.tt_trace_shadow_heightmap_indirect.argtypes = [vp, C.POINTER(ShadowParams), vp, vp, vp, vp, vp, vp]
+            for s in ["tt_scene_upload_terrains", "tt_terrain_validate", "tt_trace_heightmap",
+                      "tt_trace_heightmap_indirect", "tt_trace_shadow_heightmap", "tt_trace_shadow_heightmap_indirect"]:
+                getattr(L, s).restype = i32
         L.tt_scene_read_nodes.argtypes = [vp, u32, u32, vp]
         L.tt_scene_read_tris.argtypes = [vp, u32, u32, vp]
         L.tt_blas_refit.argtypes = [vp, C.POINTER(BlasRefitParams), vp, vp, vp]
@@ -343,6 +370,74 @@ def hip_lib():
             _bind_group(L)
         _HIP = L
     return _HIP
+
+
+# ---------------------------------------------------------------- terrains
+def _half_bits(heightmap) -> np.ndarray:
+    hm = np.ascontiguousarray(heightmap)
+    return hm.view(np.uint16) if hm.dtype == np.float16 else np.ascontiguousarray(hm, np.uint16)
+
+
+def terrain_validate(terrains, heightmap):
+    """tt_terrain_validate (host only): (status, reason) of what tt_scene_upload_terrains would answer."""
+    t = np.ascontiguousarray(terrains, TERRAIN_DTYPE)
+    hm = None if heightmap is None else _half_bits(heightmap)
+    h, w = (0, 0) if hm is None else hm.shape
+    why = C.create_string_buffer(256)
+    st = hip_lib().tt_terrain_validate(_ptr(t) if len(t) else None, len(t), _ptr(hm), w, h, why, 256)
+    return st, why.value.decode()
+
+
+def synthetic_heightmap(seed: int, w: int, h: int) -> np.ndarray:
+    """A seeded heightmap as binary16 bits (uint16 [h, w], values in [0, 1]): a few smooth sine hills plus one
+    vertical step (a cliff along a line x = const), the two shapes a heightmap march meets."""
+    rng = np.random.default_rng(seed)
+    y, x = np.meshgrid(np.arange(h, dtype=np.float64) / max(h - 1, 1), np.arange(w, dtype=np.float64) / max(w - 1, 1),
+                       indexing="ij")
+    z = np.zeros((h, w))
+    for _ in range(4):
+        fx, fy = rng.uniform(0.5, 3.0, 2)
+        px, py = rng.uniform(0.0, 2.0 * np.pi, 2)
+        z += rng.uniform(0.3, 1.0) * np.sin(2.0 * np.pi * fx * x + px) * np.sin(2.0 * np.pi * fy * y + py)
+    z = (z - z.min()) / max(z.max() - z.min(), 1e-12) * 0.6
+    z[:, x[0] > rng.uniform(0.55, 0.75)] += 0.4  # the step
+    return np.clip(z, 0.0, 1.0).astype(np.float16).view(np.uint16)
+
+
+def terrain_trace_host(terrains, heightmap, rays, n_rays, bounce, far_plane, width, height, info=None, flags=0,
+                       detail=None) -> Stats:
+    """tt_terrain_trace_(detail_)host: the scalar host reference of tt_trace_heightmap, in place on rays / info."""
+    t = np.ascontiguousarray(terrains, TERRAIN_DTYPE)
+    hm = _half_bits(heightmap)
+    p = TraceParams(n_rays=n_rays, bounce=bounce, far_plane=far_plane, screen_width=width, screen_height=height,
+                    flags=flags)
+    s = Stats()
+    _check(scene_lib().tt_terrain_trace_detail_host(_ptr(t), len(t), _ptr(hm), hm.shape[1], hm.shape[0], C.byref(p),
+                                                    _ptr(rays), _ptr(info), C.byref(s), _ptr(detail)),
+           "tt_terrain_trace_detail_host")
+    return s
+
+
+def terrain_occluded_host(terrains, heightmap, shadow_rays, n_rays):
+    """tt_terrain_occluded_host: (occluded uint8 per ray, Stats) of the host reference's shadow march."""
+    t = np.ascontiguousarray(terrains, TERRAIN_DTYPE)
+    hm = _half_bits(heightmap)
+    occ = np.zeros(n_rays, np.uint8)
+    s = Stats()
+    _check(scene_lib().tt_terrain_occluded_host(_ptr(t), len(t), _ptr(hm), hm.shape[1], hm.shape[0], _ptr(shadow_rays),
+                                                n_rays, _ptr(occ), C.byref(s)), "tt_terrain_occluded_host")
+    return occ, s
+
+
+def terrain_normal_host(terrains, heightmap, position, terrain_id: int) -> np.ndarray:
+    """tt_terrain_normal_host: GetHeightmapNormal(position, terrain_id)."""
+    t = np.ascontiguousarray(terrains, TERRAIN_DTYPE)
+    hm = _half_bits(heightmap)
+    pos = np.ascontiguousarray(position, np.float32)
+    out = np.zeros(3, np.float32)
+    _check(scene_lib().tt_terrain_normal_host(_ptr(t), len(t), _ptr(hm), hm.shape[1], hm.shape[0], _ptr(pos),
+                                              int(terrain_id), _ptr(out)), "tt_terrain_normal_host")
+    return out
 
 
 # ---------------------------------------------------------------- matrices
@@ -807,6 +902,64 @@ class Engine:
         assert a.ndim == 3 and a.shape[2] == 4
         self._check(self.L.tt_scene_upload_texture_atlas(self.h, _ptr(a), a.shape[1], a.shape[0]),
                     "tt_scene_upload_texture_atlas")
+
+    def upload_terrains(self, terrains, heightmap=None, check: bool = True):
+        """tt_scene_upload_terrains: TERRAIN_DTYPE records and the Heightmap atlas as binary16 bits (uint16, or
+        float16) [height, width]. No terrains (None or empty) clears the set."""
+        t = np.zeros(0, TERRAIN_DTYPE) if terrains is None else np.ascontiguousarray(terrains, TERRAIN_DTYPE)
+        if heightmap is None:
+            hm, w, h = None, 0, 0
+        else:
+            hm = np.ascontiguousarray(heightmap)
+            hm = hm.view(np.uint16) if hm.dtype == np.float16 else np.ascontiguousarray(hm, np.uint16)
+            assert hm.ndim == 2
+            h, w = hm.shape
+        st = self.L.tt_scene_upload_terrains(self.h, _ptr(t) if len(t) else None, len(t), _ptr(hm), w, h)
+        if check:
+            self._check(st, "tt_scene_upload_terrains")
+        return st
+
+    def trace_heightmap(self, rays, n_rays: int, bounce: int, far_plane: float, width: int, height: int, info=None,
+                        flags: int = 0, device: bool = False, stats: bool = False, check: bool = True,
+                        asynchronous: bool = False):
+        """tt_trace_heightmap (kernel_heightmap replacement): marches the uploaded terrains for the rays
+        tt_trace_closest just traced; records and info texels are rewritten in place for terrain hits."""
+        p = TraceParams(n_rays=n_rays, bounce=bounce, far_plane=far_plane, screen_width=width, screen_height=height,
+                        flags=flags | (TT_TRACE_DEVICE_PTRS if device else 0) | (TT_TRACE_STATS if stats else 0)
+                        | (TT_TRACE_ASYNC if asynchronous else 0))
+        s = Stats()
+        st = self.L.tt_trace_heightmap(self.h, C.byref(p), _ptr(rays), _ptr(info), C.byref(s))
+        if check:
+            self._check(st, "tt_trace_heightmap")
+        return (s, st) if not check else s
+
+    def trace_heightmap_indirect(self, rays, n_rays_dev, capacity: int, bounce: int, far_plane: float, width: int,
+                                 height: int, info=None, flags: int = 0, check: bool = True):
+        """tt_trace_heightmap_indirect: min(*n_rays_dev, capacity) rays; device pointers, asynchronous."""
+        p = TraceParams(n_rays=capacity, bounce=bounce, far_plane=far_plane, screen_width=width, screen_height=height,
+                        flags=flags | TT_TRACE_DEVICE_PTRS)
+        st = self.L.tt_trace_heightmap_indirect(self.h, C.byref(p), _ptr(n_rays_dev), _ptr(rays), _ptr(info))
+        if check:
+            self._check(st, "tt_trace_heightmap_indirect")
+        return st
+
+    def shadow_heightmap(self, shadow_rays, n_rays: int, bounce: int, width: int, height: int, visibility=None,
+                         colors=None, nee_pos=None, cache=None, flags: int = 0, device: bool = False,
+                         asynchronous: bool = False, n_rays_dev=None, check: bool = True):
+        """tt_trace_shadow_heightmap (kernel_shadow_heightmap replacement); with n_rays_dev the indirect form
+        (n_rays is then the capacity; device pointers, asynchronous)."""
+        p = ShadowParams(n_rays=n_rays, bounce=bounce, screen_width=width, screen_height=height,
+                         flags=flags | (TT_TRACE_DEVICE_PTRS if (device or n_rays_dev is not None) else 0)
+                         | (TT_TRACE_ASYNC if asynchronous else 0))
+        if n_rays_dev is not None:
+            st = self.L.tt_trace_shadow_heightmap_indirect(self.h, C.byref(p), _ptr(n_rays_dev), _ptr(shadow_rays),
+                                                           _ptr(visibility), _ptr(colors), _ptr(nee_pos), _ptr(cache))
+        else:
+            st = self.L.tt_trace_shadow_heightmap(self.h, C.byref(p), _ptr(shadow_rays), _ptr(visibility),
+                                                  _ptr(colors), _ptr(nee_pos), _ptr(cache))
+        if check:
+            self._check(st, "tt_trace_shadow_heightmap")
+        return st
 
     def update_nodes(self, first: int, nodes: np.ndarray):
         self._check(self.L.tt_scene_update_nodes(self.h, first, len(nodes), _ptr(nodes)), "tt_scene_update_nodes")
