@@ -187,6 +187,21 @@ namespace TrueTrace.Hip
             ushort* heightmapHalf, uint width, uint height);
         [DllImport(Lib)] public static extern unsafe TTStatus tt_terrain_validate(TtTerrain* terrains, uint n,
             ushort* heightmapHalf, uint width, uint height, byte* why, uint whyLen);
+        // GPU-resident objects and the on-device scene assembly (AssetManager.AccumulateData's Combine dispatches):
+        // tt_object_validate and the two layout calls are host arithmetic and need no device
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_object_validate(void* nodes, uint nNodes, void* tris,
+            uint nTris, uint root, byte* why, uint whyLen);
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_object_create(IntPtr ctx, void* nodes, uint nNodes, void* tris,
+            uint nTris, uint root, out IntPtr obj);
+        [DllImport(Lib)] public static extern TTStatus tt_object_get_info(IntPtr obj, out TTObjectInfo info);
+        [DllImport(Lib)] public static extern TTStatus tt_object_destroy(IntPtr obj);
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_scene_layout_objects(IntPtr* objects, uint n, uint tlasRegion,
+            uint* nodeOffsets, uint* triOffsets, out uint nNodesTotal, out uint nTrisTotal);
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_scene_layout_counts(uint* nNodes, uint* nTris, uint n,
+            uint tlasRegion, uint* nodeOffsets, uint* triOffsets, out uint nNodesTotal, out uint nTrisTotal);
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_scene_assemble_objects(IntPtr ctx, IntPtr* objects,
+            uint nObjects, void* tlasNodes, uint tlasRegion, int* tlasIndices, uint nTlas, void* meshData, uint nMesh,
+            void* materials, uint nMat);
         // kernel_heightmap / kernel_shadow_heightmap (IntersectionKernels.compute:508-710); pointers are host or HIP
         // device memory as the flags say (TT_TRACE_DEVICE_PTRS); the _indirect forms read their count on the device.
         [DllImport(Lib)] public static extern TTStatus tt_trace_heightmap(IntPtr ctx, ref TTTraceParams p, IntPtr globalRays,
@@ -661,6 +676,33 @@ namespace TrueTrace.Hip
                 Check(Native.tt_blas_refit(m_ctx, ref p, v, t, l));
         }
 
+        /// tt_object_create: one ParentObject's BLAS (nodes and AggTriangles with BLAS-local indices) resident on
+        /// this tracer's device.
+        public unsafe TrueTraceHipObject CreateObject<TNode, TTri>(TNode[] nodes, TTri[] tris, uint root = 0)
+            where TNode : unmanaged where TTri : unmanaged
+        {
+            IntPtr obj;
+            fixed (TNode* n = nodes) fixed (TTri* t = tris)
+                Check(Native.tt_object_create(m_ctx, n, (uint)nodes.Length, t, (uint)tris.Length, root, out obj));
+            return new TrueTraceHipObject(obj);
+        }
+
+        /// SetMeshTraceBuffers for a changed object set, on the device (tt_scene_assemble_objects): `objects` in
+        /// layout order (RenderQue parents, then InstanceData parents); the host supplies only the TLAS-region
+        /// nodes [0, 2 * (parents + instances)), TLASBVH8Indices, _MeshData and the materials.
+        public unsafe void AssembleScene<TNode, TMesh, TMat>(TrueTraceHipObject[] objects, TNode[] tlasNodes,
+                                                             int[] tlasIndices, TMesh[] meshData, TMat[] materials)
+            where TNode : unmanaged where TMesh : unmanaged where TMat : unmanaged
+        {
+            var h = new IntPtr[objects.Length];
+            for (int k = 0; k < h.Length; k++) h[k] = objects[k]?.Handle ?? IntPtr.Zero;
+            fixed (IntPtr* o = h) fixed (TNode* n = tlasNodes) fixed (int* i = tlasIndices)
+            fixed (TMesh* m = meshData) fixed (TMat* mt = materials)
+                Check(Native.tt_scene_assemble_objects(m_ctx, o, (uint)h.Length, n, (uint)tlasNodes.Length, i,
+                                                       (uint)tlasIndices.Length, m, (uint)meshData.Length, mt,
+                                                       (uint)materials.Length));
+        }
+
         void Check(TTStatus st)
         {
             if (st != TTStatus.Ok)
@@ -672,6 +714,59 @@ namespace TrueTrace.Hip
             if (m_ctx != IntPtr.Zero) { Native.tt_ctx_destroy(m_ctx); m_ctx = IntPtr.Zero; }
             if (m_streamRef) { m_stream.DangerousRelease(); m_streamRef = false; }
             m_stream = null;
+        }
+    }
+
+    /// tt_object_info (24 bytes).
+    [StructLayout(LayoutKind.Sequential)]
+    public struct TTObjectInfo
+    {
+        public uint nNodes, nTris;
+        public int device;
+        public uint root;
+        public ulong bytes;
+    }
+
+    /// A ParentObject's BLAS resident on a GPU (tt_object): created once (TrueTraceHipTracer.CreateObject),
+    /// assembled into any number of scenes on its device, and free to be disposed once an assembly has returned.
+    public sealed class TrueTraceHipObject : IDisposable
+    {
+        IntPtr m_obj;
+
+        internal TrueTraceHipObject(IntPtr obj) { m_obj = obj; }
+
+        public IntPtr Handle => m_obj;
+
+        public TTObjectInfo Info
+        {
+            get
+            {
+                var st = Native.tt_object_get_info(m_obj, out TTObjectInfo info);
+                if (st != TTStatus.Ok) throw new InvalidOperationException($"tt_object_get_info: {st}");
+                return info;
+            }
+        }
+
+        /// AccumulateData's running sums for `objects` behind a TLAS region of `tlasRegion` nodes: the NodeOffset /
+        /// TriOffset a host writes into its _MeshData records, and the scene's totals.
+        public static unsafe (uint[] nodeOffsets, uint[] triOffsets, uint nNodes, uint nTris) Layout(
+            TrueTraceHipObject[] objects, uint tlasRegion)
+        {
+            var h = new IntPtr[objects.Length];
+            for (int k = 0; k < h.Length; k++) h[k] = objects[k]?.Handle ?? IntPtr.Zero;
+            var no = new uint[h.Length];
+            var to = new uint[h.Length];
+            TTStatus st;
+            uint nn, nt;
+            fixed (IntPtr* o = h) fixed (uint* a = no) fixed (uint* b = to)
+                st = Native.tt_scene_layout_objects(o, (uint)h.Length, tlasRegion, a, b, out nn, out nt);
+            if (st != TTStatus.Ok) throw new InvalidOperationException($"tt_scene_layout_objects: {st}");
+            return (no, to, nn, nt);
+        }
+
+        public void Dispose()
+        {
+            if (m_obj != IntPtr.Zero) { Native.tt_object_destroy(m_obj); m_obj = IntPtr.Zero; }
         }
     }
 

@@ -258,6 +258,80 @@ tt_status tt_scene_validate(const tt_cwbvh_node* nodes, uint32_t n_nodes,
                             const tt_mesh_data* meshdata, uint32_t n_mesh,
                             const tt_material* materials, uint32_t n_mat,
                             char* why, uint32_t why_len);
+/* ------------------------------------------- GPU-resident objects, on-device scene assembly
+ * The scene-change path. tt_scene_upload takes the whole aggregated scene from the host; the reference keeps
+ * every ParentObject's node and triangle buffers on the GPU and, whenever the object set changes, lays the
+ * aggregated arrays out and fills them there (AssetManager.AccumulateData, AssetManager.cs:986-1227, with
+ * CombineNodeBuffers / CombineTriBuffers, GeneralMeshFunctions.compute:26-73). The calls below are that path:
+ * an object is created once, and adding, removing or swapping objects costs one assembly -- host work in the
+ * number of objects, TLAS nodes and mesh records, and one batched device-to-device gather.
+ *
+ * tt_object: one BLAS resident on a device -- its 80-byte nodes and 88-byte triangles with BLAS-local indices
+ * exactly as tt_blas_copy (truetrace_scene.h) returns them, plus the traversal-layout triangle records derived
+ * from them once by a kernel. It belongs to the device, not to the context that created it: any context on
+ * that device may assemble it, any number of times and into several scenes, and it may be destroyed as soon
+ * as an assembly has returned (the assembly copied it). */
+typedef struct tt_object tt_object;
+
+typedef struct tt_object_info {
+    uint32_t n_nodes;
+    uint32_t n_tris;
+    int32_t device;
+    uint32_t root;
+    uint64_t bytes;     /* HBM the object occupies (nodes, triangles, derived triangle records) */
+} tt_object_info;
+TT_STATIC_ASSERT(sizeof(tt_object_info) == 24, "tt_object_info is 24 bytes");
+
+/* The check tt_object_create runs (host only, no device needed): the BLAS-level walk of tt_scene_validate
+ * from `root` with NodeOffset = TriOffset = 0, bounded by the object's OWN counts -- every reachable child
+ * index < n_nodes, every reachable triangle index < n_tris, inner meta with child bits 1, no leaf meta
+ * spilling into the internal-child bits. Stricter than the whole-scene check, where a BLAS may reach into its
+ * neighbours: an object must stand alone. why (nullable) receives the first violation. */
+tt_status tt_object_validate(const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_cuda_triangle* tris,
+                             uint32_t n_tris, uint32_t root, char* why, uint32_t why_len);
+/* Validates (TT_ERR_INVALID_ARG, reason in tt_last_error(ctx)), copies the host arrays to ctx's device and
+ * derives the traversal records there. Synchronizes the context stream. */
+tt_status tt_object_create(tt_ctx* ctx, const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_cuda_triangle* tris,
+                           uint32_t n_tris, uint32_t root, tt_object** out);
+tt_status tt_object_get_info(const tt_object* obj, tt_object_info* info);
+tt_status tt_object_destroy(tt_object* obj);
+
+/* AccumulateData's running sums (AssetManager.cs:995, :1133-1136, :1178-1181), host arithmetic only:
+ * node_offsets[0] = tlas_region (the reference's 2 * (parents + instances)), tri_offsets[0] = 0, each later
+ * offset adds the previous object's counts; the totals are the scene's n_nodes and n_tris. A host writes
+ * these values into its _MeshData records (NodeOffset, TriOffset, and the root = NodeOffset + the object's
+ * root), as AssetManager.cs:1660-1679 does. Objects in RenderQue order: parents, then instance parents.
+ * Output pointers are nullable. tt_scene_layout_counts is the same on plain counts (no handles). */
+tt_status tt_scene_layout_objects(const tt_object* const* objects, uint32_t n, uint32_t tlas_region,
+                                  uint32_t* node_offsets, uint32_t* tri_offsets, uint32_t* n_nodes_total,
+                                  uint32_t* n_tris_total);
+tt_status tt_scene_layout_counts(const uint32_t* n_nodes, const uint32_t* n_tris, uint32_t n, uint32_t tlas_region,
+                                 uint32_t* node_offsets, uint32_t* tri_offsets, uint32_t* n_nodes_total,
+                                 uint32_t* n_tris_total);
+
+/* The device-side counterpart of tt_scene_upload. The caller supplies what changes per scene and is small --
+ * the TLAS-region nodes [0, tlas_region), TLASBVH8Indices, _MeshData and the materials (host arrays) -- and
+ * the objects, in layout order, supply everything else. Afterwards the context holds a scene whose device
+ * arrays are byte for byte those tt_scene_upload would hold for the host-concatenated arrays, and every later
+ * call (traces, tt_tlas_refit, tt_scene_update_*, tt_blas_refit, tt_ctx_share_*) behaves as after that upload.
+ * Validation never touches a triangle: the TLAS-level walk over the supplied nodes, bounded by tlas_region;
+ * every TLASBVH8Indices entry < n_mesh; every mesh record's (NodeOffset, TriOffset) equal to one object's pair
+ * of the layout, and its root a node that object's own walk validated; the 4 GiB limits of tt_scene_upload.
+ * Anything else is TT_ERR_INVALID_ARG with the reason in tt_last_error, before anything is launched. Objects
+ * of another device: TT_ERR_INVALID_ARG. Refused like tt_scene_upload on a borrower and on a lender with
+ * borrowers; a failed call leaves the context without a scene. The atlases and the terrain set survive.
+ * The gather is one kernel over all objects on the context stream (csrc/tt_assemble.hip); the environment
+ * variable TT_ASSEMBLE_FORM=memcpy (read at each call) selects three device-to-device copies per object
+ * instead, kept for measurement, with identical bytes. The gather's GPU time is one tt_timing_read entry.
+ * Synchronizes the context stream.
+ * A deformed mesh: tt_blas_refit rewrites only the aggregated arrays (as the reference's RefitMesh does), so
+ * a re-assembly reverts a deformed mesh to its object's triangles until the next tt_blas_refit. */
+tt_status tt_scene_assemble_objects(tt_ctx* ctx, const tt_object* const* objects, uint32_t n_objects,
+                                    const tt_cwbvh_node* tlas_nodes, uint32_t tlas_region,
+                                    const int32_t* tlas_indices, uint32_t n_tlas_indices,
+                                    const tt_mesh_data* meshdata, uint32_t n_mesh,
+                                    const tt_material* materials, uint32_t n_mat);
+
 /* Per-frame TLAS refit region rewrite (BVH8AggregatedBuffer.SetData at
  * AssetManager.cs:1760 / GPU refit AssetManager.cs:1821-1822). */
 tt_status tt_scene_update_nodes(tt_ctx* ctx, uint32_t first, uint32_t count,

@@ -12,10 +12,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
+#include "tt_assemble.h"
+#include "tt_assemble_host.h"
 #include "tt_device.h"
 #include "tt_refit.h"
 
@@ -252,6 +255,23 @@ struct tt_ctx {
     uint64_t read_seq = 0;               // borrower: read sections enqueued so far
     uint64_t read_waited = 0;            // borrower: reads the lender's stream already waits for
     uint64_t mut_waited = 0;             // borrower: lender mutations this stream already waits for
+};
+
+// A device-resident BLAS (tt_object_create): it belongs to its device, not to a context, and an assembly
+// copies it, so it may be destroyed any time after tt_scene_assemble_objects returned.
+struct tt_object {
+    int device = 0;
+    uint32_t n_nodes = 0, n_tris = 0, root = 0;
+    DevBuf<tt_cwbvh_node> d_nodes;    // BLAS-local indices, as tt_blas_copy returns them
+    DevBuf<tt_cuda_triangle> d_tris;
+    DevBuf<TriPos> d_tripos;          // derived once, on the GPU
+    std::vector<tt_cwbvh_node> nodes;  // host mirror: an assembled scene's host.nodes is composed from these
+    tt_asm::ObjectWalk walk;           // the nodes the BLAS walk reached, the largest MatDat it saw
+    ~tt_object() {
+        d_nodes.release();
+        d_tris.release();
+        d_tripos.release();
+    }
 };
 
 // Scene-mutating calls are refused on a borrower (update the lender), and reallocating ones on a
@@ -580,23 +600,10 @@ void remember_validation(SceneHost& h, const Validator& v) {
     for (uint32_t n : v.blas_visit) h.is_blas_node[n] = 1u;
 }
 
-tt_status check_scene(const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_cuda_triangle* tris, uint32_t n_tris,
-                      const int32_t* tlas, uint32_t n_tlas, const tt_mesh_data* md, uint32_t n_mesh,
-                      const tt_material* mats, uint32_t n_mat, SceneHost& h, std::vector<uint32_t>& tags,
-                      bool& any_invisible, std::string& why) {
-    if (!nodes || !n_nodes || !tris || !n_tris || !tlas || !n_tlas || !md || !n_mesh || (n_mat && !mats)) {
-        why = "null or empty buffer";
-        return TT_ERR_INVALID_ARG;
-    }
-    if ((uint64_t)n_nodes * std::max<uint64_t>(sizeof(tt_cwbvh_node), TT_NODE_STRIDE) >= (1ull << 32) ||
-        (uint64_t)n_tris * 48u >= (1ull << 32)) {
-        why = "node or triangle array of 4 GiB or more (the trace kernel addresses them with 32-bit offsets)";
-        return TT_ERR_INVALID_ARG;
-    }
-    h.nodes.assign(nodes, nodes + n_nodes);
-    h.tlas.assign(tlas, tlas + n_tlas);
-    h.mesh.assign(md, md + n_mesh);
-    h.n_tris = n_tris;
+// The material words and the cutout / glass records of a scene's materials (h starts out fresh), shared by the
+// two ways a scene arrives: tt_scene_upload and tt_scene_assemble_objects.
+void derive_materials(const tt_material* mats, uint32_t n_mat, SceneHost& h, std::vector<uint32_t>& tags,
+                      bool& any_invisible) {
     h.n_mat = n_mat;
     any_invisible = false;
     tags.assign(std::max<uint32_t>(n_mat, 1u), 0u);
@@ -631,6 +638,26 @@ tt_status check_scene(const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_cud
             for (int k = 0; k < 4; k++) r.scale[k] = mats[m].AlbedoTexScale[k];
         }
     }
+}
+
+tt_status check_scene(const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_cuda_triangle* tris, uint32_t n_tris,
+                      const int32_t* tlas, uint32_t n_tlas, const tt_mesh_data* md, uint32_t n_mesh,
+                      const tt_material* mats, uint32_t n_mat, SceneHost& h, std::vector<uint32_t>& tags,
+                      bool& any_invisible, std::string& why) {
+    if (!nodes || !n_nodes || !tris || !n_tris || !tlas || !n_tlas || !md || !n_mesh || (n_mat && !mats)) {
+        why = "null or empty buffer";
+        return TT_ERR_INVALID_ARG;
+    }
+    if ((uint64_t)n_nodes * std::max<uint64_t>(sizeof(tt_cwbvh_node), TT_NODE_STRIDE) >= (1ull << 32) ||
+        (uint64_t)n_tris * 48u >= (1ull << 32)) {
+        why = "node or triangle array of 4 GiB or more (the trace kernel addresses them with 32-bit offsets)";
+        return TT_ERR_INVALID_ARG;
+    }
+    h.nodes.assign(nodes, nodes + n_nodes);
+    h.tlas.assign(tlas, tlas + n_tlas);
+    h.mesh.assign(md, md + n_mesh);
+    h.n_tris = n_tris;
+    derive_materials(mats, n_mat, h, tags, any_invisible);
     if (any_invisible) {
         h.matdat.resize(n_tris);
         for (uint32_t t = 0; t < n_tris; t++) h.matdat[t] = tris[t].MatDat;
@@ -1225,6 +1252,301 @@ tt_status tt_scene_upload(tt_ctx* c, const tt_cwbvh_node* nodes, uint32_t n_node
         if ((e = c->mat_glass.alloc(h.glass.size())) != hipSuccess) return hip_fail(c, e, "glass records");
         TT_HIP(c, hipMemcpy(c->mat_glass.p, h.glass.data(), sizeof(GlassMat) * h.glass.size(), hipMemcpyHostToDevice));
     }
+    c->host = std::move(h);
+    c->n_nodes_scene = n_nodes;
+    c->n_nodes_dev = n_nodes_dev;
+    c->tlas_res = tlas_res;
+    c->ovl_used = 0;
+    c->root_known = true;
+    c->any_invisible = any_invisible;
+    c->scene_gen++;
+    c->any_shadow_skip = c->host.any_shadow_skip;
+    c->any_cutout = c->host.any_cutout;
+    c->any_atlas_shadow = c->host.any_atlas_shadow;
+    c->leaf.release();
+    {
+        const tt_status st = refresh_leaves(c);
+        if (st != TT_OK) return st;
+    }
+    c->has_scene = true;
+    return TT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- GPU-resident objects, on-device assembly
+namespace {
+// The gather's form. One batched kernel over all objects (csrc/tt_assemble.hip) is the product;
+// TT_ASSEMBLE_FORM=memcpy selects three device-to-device copies per object, kept for A/B measurement
+// (tools/assemble_bench.py, profiles/r09/assemble/). Read at every assembly -- a getenv beside a scene's worth of
+// copies -- so one process can time both forms in turn. The bytes are identical in both forms.
+bool assemble_kernel_form() {
+    const char* e = std::getenv("TT_ASSEMBLE_FORM");
+    return !(e && std::strcmp(e, "memcpy") == 0);
+}
+
+void copy_why(const std::string& w, char* why, uint32_t why_len) {
+    if (why && why_len) {
+        std::strncpy(why, w.c_str(), why_len - 1);
+        why[why_len - 1] = 0;
+    }
+}
+
+bool over_4gib(uint64_t n_nodes, uint64_t n_tris) {
+    return n_nodes * std::max<uint64_t>(sizeof(tt_cwbvh_node), TT_NODE_STRIDE) >= (1ull << 32) || n_tris * 48u >= (1ull << 32);
+}
+}  // namespace
+
+extern "C" {
+
+tt_status tt_object_validate(const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_cuda_triangle* tris, uint32_t n_tris,
+                             uint32_t root, char* why, uint32_t why_len) {
+    tt_asm::ObjectWalk w;
+    const tt_status st = tt_asm::validate_object(nodes, n_nodes, tris, n_tris, root, w);
+    copy_why(w.why, why, why_len);
+    return st;
+}
+
+tt_status tt_object_create(tt_ctx* c, const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_cuda_triangle* tris,
+                           uint32_t n_tris, uint32_t root, tt_object** out) {
+    if (!c) return TT_ERR_INVALID_ARG;
+    if (!out) return fail(c, TT_ERR_INVALID_ARG, "tt_object_create: null output handle");
+    *out = nullptr;
+    TT_REFUSE_DEAD_STREAM(c);
+    std::unique_ptr<tt_object> o(new tt_object);
+    const tt_status vs = tt_asm::validate_object(nodes, n_nodes, tris, n_tris, root, o->walk);
+    if (vs != TT_OK) return fail(c, vs, "object validation failed: %s", o->walk.why.c_str());
+    if (over_4gib(n_nodes, n_tris))
+        return fail(c, TT_ERR_INVALID_ARG, "node or triangle array of 4 GiB or more (the trace kernel addresses them with 32-bit offsets)");
+    TT_HIP(c, hipSetDevice(c->device));
+    hipError_t e;
+    if ((e = o->d_nodes.alloc(n_nodes)) != hipSuccess || (e = o->d_tris.alloc(n_tris)) != hipSuccess ||
+        (e = o->d_tripos.alloc(n_tris)) != hipSuccess)
+        return hip_fail(c, e, "object allocation");
+    TT_HIP(c, hipMemcpy(o->d_nodes.p, nodes, sizeof(tt_cwbvh_node) * n_nodes, hipMemcpyHostToDevice));
+    TT_HIP(c, hipMemcpy(o->d_tris.p, tris, sizeof(tt_cuda_triangle) * n_tris, hipMemcpyHostToDevice));
+    TT_HIP(c, tt_launch_derive_tripos(o->d_tris.p, o->d_tripos.p, n_tris, c->stream));
+    TT_HIP(c, hipStreamSynchronize(c->stream));  // any context's stream may read the object from here on
+    o->nodes.assign(nodes, nodes + n_nodes);
+    o->device = c->device;
+    o->n_nodes = n_nodes;
+    o->n_tris = n_tris;
+    o->root = root;
+    *out = o.release();
+    return TT_OK;
+}
+
+tt_status tt_object_get_info(const tt_object* o, tt_object_info* info) {
+    if (!o || !info) return TT_ERR_INVALID_ARG;
+    info->n_nodes = o->n_nodes;
+    info->n_tris = o->n_tris;
+    info->device = o->device;
+    info->root = o->root;
+    info->bytes = (uint64_t)o->n_nodes * sizeof(tt_cwbvh_node) + (uint64_t)o->n_tris * (sizeof(tt_cuda_triangle) + sizeof(TriPos));
+    return TT_OK;
+}
+
+tt_status tt_object_destroy(tt_object* o) {
+    if (!o) return TT_ERR_INVALID_ARG;
+    delete o;
+    return TT_OK;
+}
+
+tt_status tt_scene_layout_counts(const uint32_t* n_nodes, const uint32_t* n_tris, uint32_t n, uint32_t tlas_region,
+                                 uint32_t* node_offsets, uint32_t* tri_offsets, uint32_t* n_nodes_total,
+                                 uint32_t* n_tris_total) {
+    std::string why;
+    return tt_asm::layout_counts(n_nodes, n_tris, n, tlas_region, node_offsets, tri_offsets, n_nodes_total, n_tris_total, why);
+}
+
+tt_status tt_scene_layout_objects(const tt_object* const* objects, uint32_t n, uint32_t tlas_region, uint32_t* node_offsets,
+                                  uint32_t* tri_offsets, uint32_t* n_nodes_total, uint32_t* n_tris_total) {
+    if (!objects || !n) return TT_ERR_INVALID_ARG;
+    std::vector<uint32_t> nn(n), nt(n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (!objects[i]) return TT_ERR_INVALID_ARG;
+        nn[i] = objects[i]->n_nodes;
+        nt[i] = objects[i]->n_tris;
+    }
+    return tt_scene_layout_counts(nn.data(), nt.data(), n, tlas_region, node_offsets, tri_offsets, n_nodes_total, n_tris_total);
+}
+
+tt_status tt_scene_assemble_objects(tt_ctx* c, const tt_object* const* objects, uint32_t n_objects,
+                                    const tt_cwbvh_node* tlas_nodes, uint32_t tlas_region, const int32_t* tlas,
+                                    uint32_t n_tlas, const tt_mesh_data* md, uint32_t n_mesh, const tt_material* mats,
+                                    uint32_t n_mat) {
+    if (!c) return TT_ERR_INVALID_ARG;
+    TT_REFUSE_DEAD_STREAM(c);
+    TT_REFUSE_BORROWER(c);
+    TT_REFUSE_LENDER(c);
+    c->has_scene = false;
+    if (!objects || !n_objects || !tlas_nodes || !tlas_region || !tlas || !n_tlas || !md || !n_mesh || (n_mat && !mats))
+        return fail(c, TT_ERR_INVALID_ARG, "tt_scene_assemble_objects: null or empty buffer");
+    // ---- host: O(objects + TLAS + meshes) checks, nothing per triangle, and no BLAS is walked again
+    std::vector<uint32_t> cnt_n(n_objects), cnt_t(n_objects), off_n(n_objects), off_t(n_objects);
+    for (uint32_t i = 0; i < n_objects; i++) {
+        const tt_object* o = objects[i];
+        if (!o) return fail(c, TT_ERR_INVALID_ARG, "tt_scene_assemble_objects: object %u is null", i);
+        if (o->device != c->device)
+            return fail(c, TT_ERR_INVALID_ARG, "tt_scene_assemble_objects: object %u lives on device %d, the context on %d", i,
+                        o->device, c->device);
+        cnt_n[i] = o->n_nodes;
+        cnt_t[i] = o->n_tris;
+    }
+    uint32_t n_nodes = 0, n_tris = 0;
+    std::string why;
+    if (tt_asm::layout_counts(cnt_n.data(), cnt_t.data(), n_objects, tlas_region, off_n.data(), off_t.data(), &n_nodes,
+                              &n_tris, why) != TT_OK)
+        return fail(c, TT_ERR_INVALID_ARG, "tt_scene_assemble_objects: %s", why.c_str());
+    if (over_4gib(n_nodes, n_tris))
+        return fail(c, TT_ERR_INVALID_ARG, "scene validation failed: node or triangle array of 4 GiB or more (the trace kernel "
+                                           "addresses them with 32-bit offsets)");
+    for (uint32_t i = 0; i < n_tlas; i++)
+        if (tlas[i] < 0 || (uint32_t)tlas[i] >= n_mesh)
+            return fail(c, TT_ERR_INVALID_ARG, "scene validation failed: TLASBVH8Indices entry %u (%d) out of range", i, tlas[i]);
+    // every mesh record names one object by its (NodeOffset, TriOffset) pair of the layout, and a root that
+    // object's own walk reached (so the subtree below it was validated against the object's counts)
+    std::vector<uint8_t> used(n_objects, 0u);
+    std::vector<SceneHost::BlasKey> keys;
+    for (uint32_t m = 0; m < n_mesh; m++) {
+        const tt_mesh_data& r = md[m];
+        if (r.NodeOffset < 0 || r.TriOffset < 0) return fail(c, TT_ERR_INVALID_ARG, "scene validation failed: negative mesh offsets");
+        // (node offsets strictly increase: every object has nodes)
+        const uint32_t i = (uint32_t)(std::upper_bound(off_n.begin(), off_n.end(), (uint32_t)r.NodeOffset) - off_n.begin());
+        if (i == 0 || off_n[i - 1] != (uint32_t)r.NodeOffset || off_t[i - 1] != (uint32_t)r.TriOffset)
+            return fail(c, TT_ERR_INVALID_ARG, "scene validation failed: mesh record %u (NodeOffset %d, TriOffset %d) matches no "
+                                               "object of the layout", m, r.NodeOffset, r.TriOffset);
+        const tt_object* o = objects[i - 1];
+        const uint32_t root = (uint32_t)(r.mesh_data_bvh_offsets & 0x7fffffff);
+        if (root < off_n[i - 1] || root - off_n[i - 1] >= o->n_nodes || !o->walk.reach[root - off_n[i - 1]])
+            return fail(c, TT_ERR_INVALID_ARG, "scene validation failed: mesh record %u: root %u is not a validated node of its "
+                                               "object (nodes [%u, %u))", m, root, off_n[i - 1], off_n[i - 1] + o->n_nodes);
+        // (MaterialOffset + the object's largest MatDat against n_mat: check_scene computes that bound but
+        // enforces it nowhere, so neither does this path -- a scene upload accepts is accepted here)
+        used[i - 1] = 1u;
+        keys.push_back(SceneHost::BlasKey{root, (uint32_t)r.NodeOffset, (uint32_t)r.TriOffset});
+    }
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    // the host mirror, composed by memcpy; then the TLAS-level walk over the supplied nodes only
+    SceneHost h;
+    h.nodes.reserve(n_nodes);
+    h.nodes.assign(tlas_nodes, tlas_nodes + tlas_region);
+    for (uint32_t i = 0; i < n_objects; i++) h.nodes.insert(h.nodes.end(), objects[i]->nodes.begin(), objects[i]->nodes.end());
+    h.tlas.assign(tlas, tlas + n_tlas);
+    h.mesh.assign(md, md + n_mesh);
+    h.n_tris = n_tris;
+    std::vector<uint32_t> tags;
+    bool any_invisible = false;
+    derive_materials(mats, n_mat, h, tags, any_invisible);
+    // (h.matdat, upload's per-triangle MatDat copy for Invisible materials, stays empty: it feeds only the unused
+    // bound above)
+    {
+        Validator v(h);
+        v.n_tl = tlas_region;
+        if (!v.walk(0, 0, 0, true)) return fail(c, TT_ERR_INVALID_ARG, "scene validation failed: TLAS: %s", v.why.c_str());
+        h.blas_ok = keys;
+        h.tlas_nodes = v.tlas_visit;
+    }
+    h.is_tlas_node.assign(n_nodes, 0u);
+    for (uint32_t n : h.tlas_nodes) h.is_tlas_node[n] = 1u;
+    h.is_blas_node.assign(n_nodes, 0u);
+    for (uint32_t i = 0; i < n_objects; i++)
+        if (used[i]) std::memcpy(h.is_blas_node.data() + off_n[i], objects[i]->walk.reach.data(), objects[i]->n_nodes);
+    // ---- device: the buffers tt_scene_upload would hold
+    TT_HIP(c, hipSetDevice(c->device));
+    TT_HIP(c, hipStreamSynchronize(c->stream));  // nothing enqueued still reads the scene being replaced
+    std::vector<MeshGpu> mg(n_mesh);
+    for (uint32_t m = 0; m < n_mesh; m++) derive_mesh(md[m], mg[m]);
+    c->nodes.release();
+    c->tris_raw.release();
+    c->tris.release();
+    c->tlas.release();
+    c->mesh_raw.release();
+    c->mesh.release();
+    c->mat_tag.release();
+    c->mat_cut.release();
+    c->mat_glass.release();
+    uint32_t tlas_res = 0;
+    for (uint32_t n : h.tlas_nodes) tlas_res = std::max(tlas_res, n + 1u);
+    if (((uint64_t)n_nodes + (uint64_t)TT_TLAS_SLOTS * tlas_res) * TT_NODE_STRIDE >= (1ull << 32)) tlas_res = 0;
+    const uint32_t n_nodes_dev = n_nodes + TT_TLAS_SLOTS * tlas_res;
+    hipError_t e;
+    if ((e = c->nodes.alloc(n_nodes_dev)) != hipSuccess || (e = c->tris_raw.alloc(n_tris)) != hipSuccess ||
+        (e = c->tris.alloc(n_tris)) != hipSuccess || (e = c->tlas.alloc(n_tlas)) != hipSuccess ||
+        (e = c->mesh_raw.alloc(n_mesh)) != hipSuccess || (e = c->mesh.alloc(n_mesh)) != hipSuccess ||
+        (e = c->mat_tag.alloc(tags.size())) != hipSuccess)
+        return hip_fail(c, e, "scene allocation");
+    // the TLAS region from the host; the overlay regions behind the nodes stay as upload leaves them (unwritten
+    // in `nodes`, zero in the strided copy)
+    TT_HIP(c, hipMemcpy(c->nodes.p, tlas_nodes, sizeof(tt_cwbvh_node) * tlas_region, hipMemcpyHostToDevice));
+    if (TT_NODE_STRIDE != 80) {
+        c->nodes_k.release();
+        if ((e = c->nodes_k.alloc((size_t)n_nodes_dev * TT_NODE_STRIDE)) != hipSuccess) return hip_fail(c, e, "node copy");
+        TT_HIP(c, hipMemsetAsync(c->nodes_k.p, 0, (size_t)n_nodes_dev * TT_NODE_STRIDE, c->stream));
+        TT_HIP(c, refresh_node_copy(c, 0, tlas_region));
+    }
+    DevBuf<AsmSegment> table;
+    struct TableGuard {
+        DevBuf<AsmSegment>& t;
+        ~TableGuard() { t.release(); }
+    } table_guard{table};
+    std::vector<AsmSegment> seg;  // (outlives the asynchronous table copy: the stream is synchronized below)
+    uint32_t ring_slot;
+    TT_HIP(c, ring_open(c, ring_slot));  // tt_timing_read: the gather's GPU time, in either form
+    if (assemble_kernel_form()) {
+        seg.reserve((size_t)3 * n_objects);
+        uint64_t units = 0;
+        auto add = [&](const void* src, void* dst, void* dst_k, uint64_t bytes) {
+            AsmSegment g;
+            g.src = static_cast<const uint8_t*>(src);
+            g.dst = static_cast<uint8_t*>(dst);
+            g.dst_k = static_cast<uint8_t*>(dst_k);
+            g.bytes = bytes;
+            g.pad = 0;
+            g.wide = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0 ? 1u : 0u;
+            units += (bytes + 15u) / 16u;
+            g.unit_end = units;
+            seg.push_back(g);
+        };
+        for (uint32_t i = 0; i < n_objects; i++) {
+            const tt_object* o = objects[i];
+            add(o->d_nodes.p, c->nodes.p + off_n[i],
+                TT_NODE_STRIDE != 80 ? c->nodes_k.p + (size_t)off_n[i] * TT_NODE_STRIDE : nullptr,
+                (uint64_t)o->n_nodes * sizeof(tt_cwbvh_node));
+            add(o->d_tris.p, c->tris_raw.p + off_t[i], nullptr, (uint64_t)o->n_tris * sizeof(tt_cuda_triangle));
+            add(o->d_tripos.p, c->tris.p + off_t[i], nullptr, (uint64_t)o->n_tris * sizeof(TriPos));
+        }
+        if ((e = table.alloc(seg.size())) != hipSuccess) return hip_fail(c, e, "assembly table");
+        TT_HIP(c, hipMemcpyAsync(table.p, seg.data(), sizeof(AsmSegment) * seg.size(), hipMemcpyHostToDevice, c->stream));
+        TT_HIP(c, tt_launch_assemble(table.p, (uint32_t)seg.size(), units, c->stream));
+    } else {
+        for (uint32_t i = 0; i < n_objects; i++) {
+            const tt_object* o = objects[i];
+            TT_HIP(c, hipMemcpyAsync(c->nodes.p + off_n[i], o->d_nodes.p, sizeof(tt_cwbvh_node) * o->n_nodes,
+                                     hipMemcpyDeviceToDevice, c->stream));
+            TT_HIP(c, hipMemcpyAsync(c->tris_raw.p + off_t[i], o->d_tris.p, sizeof(tt_cuda_triangle) * o->n_tris,
+                                     hipMemcpyDeviceToDevice, c->stream));
+            TT_HIP(c, hipMemcpyAsync(c->tris.p + off_t[i], o->d_tripos.p, sizeof(TriPos) * o->n_tris,
+                                     hipMemcpyDeviceToDevice, c->stream));
+        }
+        TT_HIP(c, refresh_node_copy(c, tlas_region, n_nodes - tlas_region));
+    }
+    TT_HIP(c, ring_close(c, ring_slot));
+    TT_HIP(c, hipMemcpyAsync(c->tlas.p, tlas, sizeof(int32_t) * n_tlas, hipMemcpyHostToDevice, c->stream));
+    TT_HIP(c, hipMemcpyAsync(c->mesh_raw.p, md, sizeof(tt_mesh_data) * n_mesh, hipMemcpyHostToDevice, c->stream));
+    TT_HIP(c, hipMemcpyAsync(c->mesh.p, mg.data(), sizeof(MeshGpu) * n_mesh, hipMemcpyHostToDevice, c->stream));
+    TT_HIP(c, hipMemcpyAsync(c->mat_tag.p, tags.data(), sizeof(uint32_t) * tags.size(), hipMemcpyHostToDevice, c->stream));
+    if (h.any_cutout) {
+        if ((e = c->mat_cut.alloc(h.cut.size())) != hipSuccess) return hip_fail(c, e, "cutout records");
+        TT_HIP(c, hipMemcpyAsync(c->mat_cut.p, h.cut.data(), sizeof(CutoutMat) * h.cut.size(), hipMemcpyHostToDevice, c->stream));
+    }
+    if (h.any_atlas_shadow) {
+        if ((e = c->mat_glass.alloc(h.glass.size())) != hipSuccess) return hip_fail(c, e, "glass records");
+        TT_HIP(c, hipMemcpyAsync(c->mat_glass.p, h.glass.data(), sizeof(GlassMat) * h.glass.size(), hipMemcpyHostToDevice,
+                                 c->stream));
+    }
+    TT_HIP(c, hipStreamSynchronize(c->stream));  // the objects may be destroyed, the host arrays reused
     c->host = std::move(h);
     c->n_nodes_scene = n_nodes;
     c->n_nodes_dev = n_nodes_dev;

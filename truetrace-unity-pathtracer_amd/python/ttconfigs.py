@@ -71,7 +71,14 @@ def _mix_seed(seed: int, k: int) -> int:
 
 def c4_bistro(seed: int = C4_SEED, n_unique: int = 600, n_instances: int = 2400, min_tris: int = 200,
               max_tris: int = 40000) -> tthip.Scene:
-    """Two-level scene (AssetManager.cs:1714-1750): the street plane as a RenderQue parent, then
+    return c4_bistro_manager(seed, n_unique, n_instances, min_tris, max_tris)[1]
+
+
+def c4_bistro_manager(seed: int = C4_SEED, n_unique: int = 600, n_instances: int = 2400, min_tris: int = 200,
+                      max_tris: int = 40000):
+    """(AssetManager, Scene) of C4: the manager holds the BLASes the scene-change path keeps on the GPU.
+
+    Two-level scene (AssetManager.cs:1714-1750): the street plane as a RenderQue parent, then
     ``n_unique`` InstanceData parents (facades/props from ``tt_synth_prop``, tri counts
     log-uniform in [min_tris, max_tris]) and ``n_instances`` InstancedObjects dealt round-robin
     over them, placed 12-20 m off the centre lines of a 40 m street grid over [-100, 100]^2
@@ -102,11 +109,16 @@ def c4_bistro(seed: int = C4_SEED, n_unique: int = 600, n_instances: int = 2400,
     sc = am.build()
     sc.meta.update({"unique_blas": n_unique, "instances": n_instances,
                     "unique_tris": int(len(sc.tris)), "instanced_tris": int(sizes[np.arange(n_instances) % n_unique].sum())})
-    return sc
+    return am, sc
 
 
 def c5_san_miguel(seed: int = C5_SEED, n_tris: int = C5_TRIS) -> tthip.Scene:
     """One ParentObject with ``n_tris`` triangles (the San Miguel OBJ imports as one mesh)."""
+    return c5_san_miguel_manager(seed, n_tris)[1]
+
+
+def c5_san_miguel_manager(seed: int = C5_SEED, n_tris: int = C5_TRIS):
+    """(AssetManager, Scene) of C5."""
     am = tthip.AssetManager()
     am.add_parent(tthip.Blas(tthip.Mesh.san_miguel(seed, n_tris)), None, np.zeros(8, tthip.MAT_DTYPE))
-    return am.build()
+    return am, am.build()

@@ -166,6 +166,11 @@ class SceneBuildInfo(C.Structure):
                 ("n_mesh", C.c_uint32), ("tlas_nodes", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class ObjectInfo(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint32), ("n_tris", C.c_uint32), ("device", C.c_int32), ("root", C.c_uint32),
+                ("bytes", C.c_uint64)]
+
+
 class TTError(RuntimeError):
     def __init__(self, status: int, msg: str = ""):
         super().__init__(f"{STATUS_NAMES.get(status, status)}: {msg}")
@@ -199,7 +204,8 @@ HIP_SYMBOLS = ["tt_abi_version", "tt_device_count", "tt_ctx_create", "tt_ctx_des
                "tt_trace_shadow_ex_indirect", "tt_timing_reset", "tt_timing_read", "tt_scene_validate", "tt_trace_diagnostics",
                "tt_selftest_rcp", "tt_trace_closest_hits", "tt_ctx_share_scene", "tt_scene_upload_terrains",
                "tt_terrain_validate", "tt_trace_heightmap", "tt_trace_heightmap_indirect", "tt_trace_shadow_heightmap",
-               "tt_trace_shadow_heightmap_indirect"]
+               "tt_trace_shadow_heightmap_indirect", "tt_object_validate", "tt_object_create", "tt_object_get_info",
+               "tt_object_destroy", "tt_scene_layout_objects", "tt_scene_layout_counts", "tt_scene_assemble_objects"]
 SCENE_SYMBOLS = ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_blas_free", "tt_scene_assemble",
                  "tt_scene_build_get_info", "tt_scene_build_copy", "tt_scene_build_free", "tt_pack_octahedral",
                  "tt_bvh2_build", "tt_dotnet_sort_by_key", "tt_synth_cornell", "tt_synth_soup", "tt_synth_sponza",
@@ -325,6 +331,17 @@ def hip_lib():
             L.tt_trace_shadow_heightmap_indirect.argtypes = [vp, C.POINTER(ShadowParams), vp, vp, vp, vp, vp, vp]
             for s in ["tt_scene_upload_terrains", "tt_terrain_validate", "tt_trace_heightmap",
                       "tt_trace_heightmap_indirect", "tt_trace_shadow_heightmap", "tt_trace_shadow_heightmap_indirect"]:
+                getattr(L, s).restype = i32
+        if hasattr(L, "tt_object_create"):  # (absent from older variant libraries)
+            L.tt_object_validate.argtypes = [vp, u32, vp, u32, u32, C.c_char_p, u32]
+            L.tt_object_create.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(vp)]
+            L.tt_object_get_info.argtypes = [vp, C.POINTER(ObjectInfo)]
+            L.tt_object_destroy.argtypes = [vp]
+            L.tt_scene_layout_objects.argtypes = [vp, u32, u32, vp, vp, C.POINTER(u32), C.POINTER(u32)]
+            L.tt_scene_layout_counts.argtypes = [vp, vp, u32, u32, vp, vp, C.POINTER(u32), C.POINTER(u32)]
+            L.tt_scene_assemble_objects.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32]
+            for s in ["tt_object_validate", "tt_object_create", "tt_object_get_info", "tt_object_destroy",
+                      "tt_scene_layout_objects", "tt_scene_layout_counts", "tt_scene_assemble_objects"]:
                 getattr(L, s).restype = i32
         L.tt_scene_read_nodes.argtypes = [vp, u32, u32, vp]
         L.tt_scene_read_tris.argtypes = [vp, u32, u32, vp]
@@ -765,6 +782,21 @@ class AssetManager:
         materials = np.concatenate(mats) if mats else np.zeros(1, MAT_DTYPE)
         return Scene(nodes, tris, tlas, md, materials, tlas_nodes=info.tlas_nodes, meta={"mesh_aabbs": aabbs})
 
+    def blases(self) -> List:
+        """The BLASes in layout order (AccumulateData): RenderQue parents, then InstanceData parents."""
+        return [p[0] for p in self.parents] + [p[0] for p in self.instance_parents]
+
+    def assemble(self, engine: "Engine", objects=None):
+        """The scene-change path: the TLAS side is built on the host as build() does, the BLAS side is gathered on
+        the device from one GPU-resident object per BLAS (`objects` in blases() order; created here when None).
+        Returns (Scene, objects): the host Scene is what tt_scene_upload would have taken."""
+        s = self.build()
+        if objects is None:
+            objects = [engine.create_object(b) for b in self.blases()]
+        region = 2 * len(s.meshdata)  # AssetManager.cs:995: the TLAS region in front of the first object
+        engine.assemble(objects, s.nodes[:region], s.tlas, s.meshdata, s.materials)
+        return s, objects
+
 
 def single_object_scene(mesh: Mesh, local_to_world=None, n_materials: int = 8) -> Scene:
     am = AssetManager()
@@ -803,6 +835,59 @@ def tlas_root_form(node0) -> int:
     if st != TT_OK:
         raise TTError(st, "tt_tlas_root_form")
     return int(f.value)
+
+
+class SceneObject:
+    """tt_object: one BLAS resident on a device (Engine.create_object). An assembly copies it, so it may be
+    destroyed as soon as Engine.assemble has returned."""
+
+    def __init__(self, L, handle: int):
+        self.L, self.h = L, handle
+
+    @property
+    def info(self) -> ObjectInfo:
+        info = ObjectInfo()
+        _check(self.L.tt_object_get_info(self.h, C.byref(info)), "tt_object_get_info")
+        return info
+
+    def destroy(self):
+        if getattr(self, "h", None):
+            self.L.tt_object_destroy(self.h)
+            self.h = None
+
+    __del__ = destroy
+
+
+def _object_handles(objects):
+    """A C array of tt_object* from SceneObjects (None -> NULL)."""
+    return (C.c_void_p * max(1, len(objects)))(*[o.h if o is not None else None for o in objects])
+
+
+def object_validate(nodes: np.ndarray, tris: np.ndarray, root: int = 0):
+    """tt_object_validate (host only): (status, first violation) of one BLAS's arrays against its own counts."""
+    nodes, tris = np.ascontiguousarray(nodes, NODE_DTYPE), np.ascontiguousarray(tris, TRI_DTYPE)
+    why = C.create_string_buffer(256)
+    st = hip_lib().tt_object_validate(_ptr(nodes), len(nodes), _ptr(tris), len(tris), int(root), why, 256)
+    return st, why.value.decode()
+
+
+def scene_layout(objects, tlas_region: int):
+    """tt_scene_layout_objects / _counts: AccumulateData's running sums over SceneObjects, or over plain
+    (n_nodes, n_tris) pairs (host only). Returns (node_offsets, tri_offsets, n_nodes_total, n_tris_total)."""
+    L = hip_lib()
+    n = len(objects)
+    no, to = np.zeros(max(1, n), np.uint32), np.zeros(max(1, n), np.uint32)
+    tn, tt = C.c_uint32(), C.c_uint32()
+    if n and all(isinstance(o, SceneObject) for o in objects):
+        st = L.tt_scene_layout_objects(_object_handles(objects), n, int(tlas_region), _ptr(no), _ptr(to), C.byref(tn),
+                                       C.byref(tt))
+        _check(st, "tt_scene_layout_objects")
+    else:
+        cn = np.ascontiguousarray([o[0] for o in objects], np.uint32)
+        ct = np.ascontiguousarray([o[1] for o in objects], np.uint32)
+        st = L.tt_scene_layout_counts(_ptr(cn), _ptr(ct), n, int(tlas_region), _ptr(no), _ptr(to), C.byref(tn), C.byref(tt))
+        _check(st, "tt_scene_layout_counts")
+    return no[:n].copy(), to[:n].copy(), int(tn.value), int(tt.value)
 
 
 class Engine:
@@ -889,6 +974,29 @@ class Engine:
             self.upload_alpha_atlas(s.alpha_atlas)
         if s.texture_atlas is not None:
             self.upload_texture_atlas(s.texture_atlas)
+
+    def create_object(self, blas_or_arrays, root: int = 0) -> "SceneObject":
+        """tt_object_create: one BLAS (a Blas, or its (nodes, tris) arrays with BLAS-local indices) resident on this
+        engine's device. The handle belongs to the device: any engine there may assemble it."""
+        nodes, tris = blas_or_arrays.arrays() if isinstance(blas_or_arrays, Blas) else blas_or_arrays
+        nodes, tris = np.ascontiguousarray(nodes, NODE_DTYPE), np.ascontiguousarray(tris, TRI_DTYPE)
+        h = C.c_void_p()
+        self._check(self.L.tt_object_create(self.h, _ptr(nodes), len(nodes), _ptr(tris), len(tris), int(root),
+                                            C.byref(h)), "tt_object_create")
+        return SceneObject(self.L, h.value)
+
+    def assemble(self, objects, tlas_nodes: np.ndarray, tlas: np.ndarray, meshdata: np.ndarray, materials: np.ndarray):
+        """tt_scene_assemble_objects: the scene tt_scene_upload would hold for the host-concatenated arrays, gathered
+        on the device from `objects` (layout order) under the TLAS-region nodes, TLASBVH8Indices, _MeshData and
+        materials given here."""
+        tlas_nodes = np.ascontiguousarray(tlas_nodes, NODE_DTYPE)
+        tlas = np.ascontiguousarray(tlas, np.int32)
+        meshdata = np.ascontiguousarray(meshdata, MESH_DTYPE)
+        materials = np.ascontiguousarray(materials, MAT_DTYPE)
+        st = self.L.tt_scene_assemble_objects(self.h, _object_handles(objects), len(objects), _ptr(tlas_nodes),
+                                              len(tlas_nodes), _ptr(tlas), len(tlas), _ptr(meshdata), len(meshdata),
+                                              _ptr(materials), len(materials))
+        self._check(st, "tt_scene_assemble_objects")
 
     def upload_alpha_atlas(self, atlas: np.ndarray):
         """_AlphaAtlas (AssetManager.cs:260-262): R8 texels, row 0 = v in [0, 1/height)."""
