@@ -1,6 +1,7 @@
 """Context / stream lifecycle on the GPU: the library's own teardown of dedicated streams a host never
-destroyed, and the TT_ROOT_LEAF fast path's bookkeeping across scene updates (tt_api.hip: the host's copy
-of node 0 is trusted after an upload or an update of node 0, and not after a device-side TLAS refit)."""
+destroyed, and the TT_ROOT_LEAF fast path's bookkeeping across scene updates (tt_scene_api.hip sets it,
+tt_dispatch.hip reads it: the host's copy of node 0 is trusted after an upload or an update of node 0, and not
+after a device-side TLAS refit)."""
 import os
 import shutil
 import subprocess

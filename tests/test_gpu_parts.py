@@ -248,7 +248,7 @@ def test_shared_scene_sections_from_two_threads():
     section, so every borrower trace sees the scene between two whole calls: its records equal those of
     one of the four states the lender passes through ((_MeshData, TLAS boxes) of pose a / b: a+a, b+a after
     the records' rewrite, b+b after the refit, a+b, ...) exactly.
-    The borrower records no event per launch (tt_api.hip SceneRead); the lender records one on the
+    The borrower records no event per launch (tt_ctx.h SceneRead); the lender records one on the
     borrower's stream per mutation."""
     import threading
 
@@ -516,7 +516,7 @@ def test_batched_frames_equal_frames_traced_alone(cycle):
 
 def test_enqueue_counter_blocks_survive_empty_and_indirect_calls():
     """The bounce enqueue uses two counter blocks in turn, each launch zeroing the other for the next one
-    (tt_api.hip enqueue_call). Real, empty (0 rays), indirect (device count) and real calls in a mixed sequence
+    (tt_dispatch.hip enqueue_call). Real, empty (0 rays), indirect (device count) and real calls in a mixed sequence
     on one context must each return the count and the records of a fresh context's single enqueue."""
     import torch
 

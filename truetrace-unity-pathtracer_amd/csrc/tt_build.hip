@@ -28,11 +28,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "../../include/truetrace_hip.h"
-
-extern "C" hipStream_t tt_ctx_stream_of(tt_ctx* c);  // tt_api.hip (C linkage there)
-extern "C" hipError_t tt_ctx_bind_device(tt_ctx* c);  // hipSetDevice(the context's device)
-extern "C" void tt_ctx_set_error(tt_ctx* c, const char* msg);
+#include "tt_ctx.h"
 
 namespace {
 thread_local char g_err[256];  // the failing step of the current build, for tt_last_error
@@ -1077,11 +1073,11 @@ extern "C" tt_status tt_bvh2_build_device(tt_ctx* ctx, const float* aabbs, uint3
                                           uint32_t* node_count, uint32_t* max_depth) {
     tt_status s = check_inputs(ctx, aabbs, n, presorted);
     if (s != TT_OK || !final_indices) return s != TT_OK ? s : TT_ERR_INVALID_ARG;
-    TT_BH(tt_ctx_bind_device(ctx));  // allocations and launches on the context's GPU
-    hipStream_t st = tt_ctx_stream_of(ctx);
+    TT_BH(hipSetDevice(ctx->device));  // allocations and launches on the context's GPU
+    hipStream_t st = ctx->stream;
     Bvh2Dev R;
     if ((s = bvh2_stage(st, aabbs, (int)n, presorted, R)) != TT_OK) {
-        tt_ctx_set_error(ctx, g_err);
+        ctx->err = g_err;
         return s;
     }
     const size_t n2 = 2 * (size_t)n;
@@ -1103,7 +1099,7 @@ extern "C" tt_status tt_blas_build_device(tt_ctx* ctx, const float* aabbs, uint3
                                           int32_t* cwbvh_indices, uint32_t* bvh2_depth) {
     g_err[0] = 0;
     const tt_status s = blas_device(ctx, aabbs, n, presorted, nodes, max_nodes, n_nodes, cwbvh_indices, bvh2_depth);
-    if (s != TT_OK) tt_ctx_set_error(ctx, g_err[0] ? g_err : "tt_blas_build_device: invalid argument");
+    if (s != TT_OK && ctx) ctx->err = g_err[0] ? g_err : "tt_blas_build_device: invalid argument";
     return s;
 }
 
@@ -1113,8 +1109,8 @@ static tt_status blas_device(tt_ctx* ctx, const float* aabbs, uint32_t n, const 
     tt_status s = check_inputs(ctx, aabbs, n, presorted);
     if (s != TT_OK) return s;
     if (!nodes || !n_nodes || !cwbvh_indices) return TT_ERR_INVALID_ARG;
-    TT_BH(tt_ctx_bind_device(ctx));  // allocations and launches on the context's GPU
-    hipStream_t st = tt_ctx_stream_of(ctx);
+    TT_BH(hipSetDevice(ctx->device));  // allocations and launches on the context's GPU
+    hipStream_t st = ctx->stream;
     Bvh2Dev B;
     if ((s = bvh2_stage(st, aabbs, (int)n, presorted, B)) != TT_OK) return s;
     const size_t n2 = 2 * (size_t)n;
@@ -1308,11 +1304,11 @@ static tt_status presort_device(hipStream_t st, const float* aabbs, int n, int32
 extern "C" tt_status tt_bvh2_presort_device(tt_ctx* ctx, const float* aabbs, uint32_t n, int32_t* presorted) {
     if (!ctx || !aabbs || !n || !presorted || n >= (1u << 29)) return TT_ERR_INVALID_ARG;
     g_err[0] = 0;
-    if (tt_ctx_bind_device(ctx) != hipSuccess) {  // allocations and launches on the context's GPU
-        tt_ctx_set_error(ctx, "tt_bvh2_presort_device: hipSetDevice failed");
+    if (hipSetDevice(ctx->device) != hipSuccess) {  // allocations and launches on the context's GPU
+        ctx->err = "tt_bvh2_presort_device: hipSetDevice failed";
         return TT_ERR_HIP;
     }
-    const tt_status s = presort_device(tt_ctx_stream_of(ctx), aabbs, (int)n, presorted);
-    if (s != TT_OK) tt_ctx_set_error(ctx, g_err[0] ? g_err : "tt_bvh2_presort_device failed");
+    const tt_status s = presort_device(ctx->stream, aabbs, (int)n, presorted);
+    if (s != TT_OK) ctx->err = g_err[0] ? g_err : "tt_bvh2_presort_device failed";
     return s;
 }

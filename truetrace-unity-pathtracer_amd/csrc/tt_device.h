@@ -27,7 +27,7 @@ __device__ __forceinline__ float rcp_rn(float a) {
 }
 
 // Byte stride of the node array the kernels read (tt_traverse.h node_offset): 80 = the reference's
-// cwbvh_nodes as uploaded; 128 = a derived copy, one node per 128-B line (tt_api.hip keeps it in step).
+// cwbvh_nodes as uploaded; 128 = a derived copy, one node per 128-B line (tt_scene_api.hip keeps it in step).
 #ifndef TT_NODE_STRIDE
 #define TT_NODE_STRIDE 80
 #endif
@@ -131,7 +131,7 @@ struct MatView {
 // such as an imported OBJ (C2, C3, C5). Its node step (IntersectionKernels.compute:157-187, the first of
 // every ray, at t_max = FarPlane) is then that one child's slab test (tt_trace.hip root_leaf_hit, the
 // node test's arithmetic for that child), so hits, Reps and stats are unchanged. Derived on the host
-// from the node-0 bytes the device holds (tt_api.hip: known after an upload or a node update; a device
+// from the node-0 bytes the device holds (tt_ctx.h root_known: known after an upload or a node update; a device
 // refit of the TLAS turns it off until the next update), passed as a kernel argument (SGPRs).
 #ifndef TT_ROOT_LEAF
 #define TT_ROOT_LEAF 1

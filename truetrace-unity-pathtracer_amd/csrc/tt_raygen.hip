@@ -15,6 +15,7 @@
 //  * sincos in the cosine-lobe sample is pinned (sincos_pinned): HLSL leaves its precision to
 //    the driver, so both sides evaluate the same float polynomials with explicit FMAs.
 #include "tt_device.h"
+#include "tt_launch.h"
 
 namespace {
 

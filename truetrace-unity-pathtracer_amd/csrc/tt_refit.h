@@ -1,4 +1,4 @@
-// tt_refit.h — refit plans (host) and device state shared by tt_refit.hip and tt_api.hip: the TLAS
+// tt_refit.h — refit plans (host) and device state shared by tt_refit.hip and tt_scene_api.hip: the TLAS
 // refit (AssetManager.RefitTLAS) and the BLAS refit of deforming / skinned meshes
 // (ParentObject.RefitMesh), which share NodeInitializer / layer refit / NodeUpdate / NodeCompress.
 #ifndef TT_REFIT_H

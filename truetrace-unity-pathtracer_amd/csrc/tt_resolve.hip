@@ -3,6 +3,7 @@
 // (RayTracingShader.compute:111-118), both through Inverse = transpose((float3x3)W2L).
 // Not part of the trace hot loop; it exists so "normals within 1e-5" is checkable at the
 // boundary. One ray per lane, HBM-bound (48 B ray + 88 B triangle + 64 B W2L in, 24 B out).
+#include "tt_launch.h"
 #include "tt_terrain.h"
 
 namespace {

@@ -1,6 +1,7 @@
 // tt_selftest.hip — on-device self-test of the kernels' fast reciprocal (rcp_rn, tt_device.h)
 // against the correctly rounded IEEE division over every fp32 bit pattern.
 #include "tt_device.h"
+#include "tt_launch.h"
 
 namespace {
 __global__ void tt_rcp_check_kernel(uint32_t hi, unsigned long long* bad) {

@@ -20,6 +20,7 @@
 //  * TT_SHADOW_VISIBILITY_CHECK: VisabilityCheckCompute (CommonData.cginc:710-819) -- the Reps
 //    bound counts as visible and only the visibility is written.
 #include "tt_encode.h"
+#include "tt_launch.h"
 #include "tt_wide.h"
 
 namespace {

@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "tt_encode.h"
+#include "tt_launch.h"
 #include "tt_terrain.h"
 #include "tt_traverse.h"
 

@@ -14,6 +14,7 @@
 //  * the per-ray visit order, the culling distance and the strict t < best.t acceptance are
 //    exactly the reference's, so t / primID / instID are bit-identical to the oracle.
 // Numerics follow include/truetrace_hip.h (compiled with -ffp-contract=off).
+#include "tt_launch.h"
 #include "tt_wide.h"
 
 // TT_REFILL_MIN of the leaf-TLAS kernels (trace_body<LEAF>), whose ray start is cheaper: a knob of its own
@@ -641,14 +642,14 @@ __global__ TT_LEAF_BOUNDS void tt_trace_leaf_kernel(TraceArgs A) {
 template <bool S, bool M, int I>
 static hipError_t launch_one(const TraceArgs& a, bool leaf, uint32_t grid, hipStream_t st) {
     if constexpr (!S && !M) {
-        if (leaf) {  // never with stats, the material check or the adaptive order (tt_api.hip decides)
+        if (leaf) {  // never with stats, the material check or the adaptive order (tt_dispatch.hip decides)
             if (a.n_rays_dev) hipLaunchKernelGGL((tt_trace_leaf_kernel<true, I>), dim3(grid), dim3(TT_BLOCK), 0, st, a);
             else hipLaunchKernelGGL((tt_trace_leaf_kernel<false, I>), dim3(grid), dim3(TT_BLOCK), 0, st, a);
             return hipGetLastError();
         }
     }
     if constexpr (!S) {
-        if (a.n_rays_dev) {  // stats launches never take a device count (tt_api.hip refuses them)
+        if (a.n_rays_dev) {  // stats launches never take a device count (tt_dispatch.hip refuses them)
             hipLaunchKernelGGL((tt_trace_kernel_indirect<M, I>), dim3(grid), dim3(TT_BLOCK), 0, st, a);
             return hipGetLastError();
         }

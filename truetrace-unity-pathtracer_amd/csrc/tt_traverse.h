@@ -130,7 +130,7 @@ __device__ __forceinline__ uint32_t buffer_load4(__amdgpu_buffer_rsrc_t r, uint3
 }
 // i * 80 and i * 48 as shift-adds: written plainly, LLVM folds them back into v_mul_lo_u32, a
 // quarter-rate instruction on the traversal's critical path. TT_NODE_STRIDE 128: the kernels read a
-// derived copy of the node array with every 80-B node at the start of its own 128-B line (tt_api.hip
+// derived copy of the node array with every 80-B node at the start of its own 128-B line (tt_scene_api.hip
 // keeps it in step with the reference array), so a node visit touches one cache line instead of 1.5.
 static_assert(TT_NODE_STRIDE == 80 || TT_NODE_STRIDE == 128, "node stride: 80 (the reference array) or 128");
 __device__ __forceinline__ uint32_t node_offset(uint32_t i) {
