@@ -33,11 +33,38 @@ from isa_blocks import parse  # noqa: E402
 
 CSRC = os.path.join(REPO, "truetrace-unity-pathtracer_amd", "csrc")
 KERNELS = {"1": "_Z15tt_trace_kernelILb0ELb0ELi1EEv9TraceArgs", "2": "_Z15tt_trace_kernelILb0ELb0ELi2EEv9TraceArgs"}
-# source regions (file: line ranges) of the node step and the triangle pass (node_intersect / intersect_triangle
-# are inlined: their instructions carry tt_traverse.h lines)
-NODE = [("tt_traverse.h", 139, 208), ("tt_trace.hip", 423, 459)]
-TRI = [("tt_traverse.h", 292, 390), ("tt_trace.hip", 475, 486)]
+# source regions (file: line ranges) of the node step and the triangle pass: the lines between the
+# `// valu_mix:node:begin` / `:end` and `// valu_mix:tri:begin` / `:end` comment pairs of these sources, looked up
+# when the tool runs (node_intersect / intersect_triangle are inlined: their instructions carry tt_traverse.h lines)
+MARKED = ("tt_traverse.h", "tt_trace.hip")
+MARK = re.compile(r"//\s*valu_mix:(node|tri):(begin|end)\b")
 WIDE = [("tt_wide.h", 1, 10000)]
+
+
+def marked_regions(csrc=CSRC, files=MARKED):
+    """{"node": [(file, first line, last line), ...], "tri": [...]} from the marker comments."""
+    out = {"node": [], "tri": []}
+    for f in files:
+        begun = {}
+        for no, ln in enumerate(open(os.path.join(csrc, f)), 1):
+            m = MARK.search(ln)
+            if not m:
+                continue
+            name, edge = m.groups()
+            if edge == "begin":
+                if name in begun:
+                    raise SystemExit(f"{f}:{no}: valu_mix:{name}:begin inside the region begun at line {begun[name]}")
+                begun[name] = no
+            else:
+                if name not in begun:
+                    raise SystemExit(f"{f}:{no}: valu_mix:{name}:end without a begin")
+                out[name].append((f, begun.pop(name), no))
+        for name, no in begun.items():
+            raise SystemExit(f"{f}:{no}: valu_mix:{name}:begin without an end")
+    for name in out:
+        if not any(f == "tt_trace.hip" for f, _, _ in out[name]):
+            raise SystemExit(f"no valu_mix:{name} region marked in tt_trace.hip")
+    return out
 FAST = ("v_fma_f32", "v_fmac_f32", "v_mul_f32", "v_add_f32", "v_sub_f32", "v_subrev_f32", "v_and_b32", "v_or_b32",
         "v_xor_b32", "v_add_u32", "v_sub_u32", "v_subrev_u32", "v_mov_b32", "v_cndmask_b32", "v_not_b32",
         "v_add_co_u32", "v_addc_co_u32", "v_sub_co_u32", "v_mul_lo_u32", "v_readfirstlane_b32", "v_nop")
@@ -80,9 +107,9 @@ def cost_of(op, table):
     return slow, "slow"
 
 
-def region_of(block):
+def region_of(block, marked):
     lines = block["lines"]
-    for name, rules in (("wide", WIDE), ("node", NODE), ("tri", TRI)):
+    for name, rules in (("wide", WIDE), ("node", marked["node"]), ("tri", marked["tri"])):
         if any(f == fl and lo <= ln <= hi for (fl, ln) in lines for f, lo, hi in rules):
             return name
     return "rest"
@@ -100,6 +127,7 @@ def main():
                         "-ffp-contract=off", "-fno-slp-vectorize", "-gline-tables-only",
                         os.path.join(CSRC, "tt_trace.hip"), "-o", a.isa], check=True)
     table = costs()
+    marked = marked_regions()
     diag = json.load(open(a.diag))["launches"]
     units = json.load(open(a.units))
     out = {}
@@ -107,7 +135,7 @@ def main():
         blocks = parse(a.isa, sym)
         ops = collections.defaultdict(collections.Counter)
         for b in blocks:
-            ops[region_of(b)].update(b["ops"])
+            ops[region_of(b, marked)].update(b["ops"])
         d = diag[f"bounce{int(info) - 1}"]["per_ray"]
         per_ray = {"node": d["node_steps"], "tri": d["tri_passes"]}
         kname = next(k for k in units["per_kernel"] if k.endswith(f"false, false, {info}>"))

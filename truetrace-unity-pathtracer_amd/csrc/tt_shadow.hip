@@ -31,43 +31,21 @@ template <bool MATCHECK>
 __device__ __forceinline__ bool shadow_triangle(__amdgpu_buffer_rsrc_t tris, const MatView& M, int32_t tri_id,
                                                 int32_t mat_offset, const LaneRay& r, float max_distance,
                                                 float3& thr) {
-    const uint32_t to = tri_offset((uint32_t)tri_id);
-    const uint4 a = buffer_load16(tris, to), b = buffer_load16(tris, to + 16u);
-    uint2 c;
-    if (MATCHECK) {
-        c = buffer_load8(tris, to + 32u);
-    } else {
-        c.x = buffer_load4(tris, to + 32u);
-        c.y = 0u;
-    }
-    const float p0x = __uint_as_float(a.x), p0y = __uint_as_float(a.y), p0z = __uint_as_float(a.z);
-    const float e1x = __uint_as_float(a.w), e1y = __uint_as_float(b.x), e1z = __uint_as_float(b.y);
-    const float e2x = __uint_as_float(b.z), e2y = __uint_as_float(b.w), e2z = __uint_as_float(c.x);
-    const float hx = fma_(r.dy, e2z, -(r.dz * e2y));
-    const float hy = fma_(r.dz, e2x, -(r.dx * e2z));
-    const float hz = fma_(r.dx, e2y, -(r.dy * e2x));
-    const float aa = fma_(e1z, hz, fma_(e1y, hy, e1x * hx));
-    const float f = rcp_rn(aa);
-    const float sx = r.ox - p0x, sy = r.oy - p0y, sz = r.oz - p0z;
-    const float u = f * fma_(sz, hz, fma_(sy, hy, sx * hx));
-    const float qx = fma_(sy, e1z, -(sz * e1y));
-    const float qy = fma_(sz, e1x, -(sx * e1z));
-    const float qz = fma_(sx, e1y, -(sy * e1x));
-    const float v = f * fma_(r.dz, qz, fma_(r.dy, qy, r.dx * qx));
-    const float t = f * fma_(e2z, qz, fma_(e2y, qy, e2x * qx));
-    const bool in_tri = (u >= 0.0f) && (v >= 0.0f && u + v <= 1.0f);  // u <= 1 implied (tt_traverse.h)
-    bool occ = in_tri && (t > 0.0f && t < max_distance);
+    const TriData d = triangle_load<MATCHECK, 0>(tris, tri_id);
+    const TriHit h = triangle_hit(d, r);
+    const bool in_tri = TT_IN_TRIANGLE(h.u, h.v);
+    bool occ = in_tri && (h.t > 0.0f && h.t < max_distance);
     if (MATCHECK && in_tri) {
         // IsBackground / ShadowCaster surfaces never occlude (:612); Cutout with the point sampler
         // (:613-616); out-of-range material = zeros
-        const uint32_t mi = (uint32_t)(mat_offset + (int32_t)c.y);
+        const uint32_t mi = (uint32_t)(mat_offset + (int32_t)d.c.y);
         const uint32_t w = mi < M.n_mat ? M.word[mi] : 0u;
         const bool glass = (w >> TT_MATWORD_GLASS) & 1u, cutout = (w >> TT_MATWORD_CUTOUT) & 1u;
         if (((w >> TT_FLAG_IS_BACKGROUND) | (w >> TT_FLAG_SHADOW_CASTER)) & 1u) {
             occ = false;
         } else if (glass || (occ && cutout)) {
             // the alpha test comes first (:616); a glass surface that passes it tints (:621-622)
-            const float2 buv = base_uv(M, tri_id, u, v);
+            const float2 buv = base_uv(M, tri_id, h.u, h.v);
             bool rejected = false;
             if (cutout) {
                 const CutoutMat cm = M.cut[mi];
@@ -87,15 +65,9 @@ __device__ __forceinline__ bool shadow_triangle(__amdgpu_buffer_rsrc_t tris, con
     return occ;
 }
 
-struct ShadowWide {
-    LaneRay ray, wray;
+struct ShadowWide : DrainRay {
     float max_distance;
     float3 thr;
-    uint2 cg, tg;
-    uint32_t oct;
-    int32_t stack_size, tlas_ss, NodeOffset, TriOffset, MatOffset, Reps;
-    uint32_t ray_index, scol, gcol;
-    bool active;
 };
 
 struct ShadowCounters {
@@ -104,39 +76,11 @@ struct ShadowCounters {
 
 template <int GN>
 __device__ __forceinline__ void regroup_shadow(ShadowWide& s, uint64_t lead, uint32_t lane) {
-    const uint32_t grp = lane / GN;
-    uint32_t src = 0;
-    bool has = false;
-    uint64_t m = lead;
-    for (uint32_t r = 0; m; r++) {  // wave-uniform: at most 32 leaders
-        const uint32_t b = (uint32_t)__builtin_ctzll(m);
-        m &= m - 1;
-        if (grp == r) {
-            src = b;
-            has = true;
-        }
-    }
-    shfl_ray(s.ray, src);
-    shfl_ray(s.wray, src);
+    const uint32_t src = regroup_ray<GN>(s, lead, lane);
     s.max_distance = shfl_f(s.max_distance, src);
     s.thr.x = shfl_f(s.thr.x, src);
     s.thr.y = shfl_f(s.thr.y, src);
     s.thr.z = shfl_f(s.thr.z, src);
-    s.cg.x = shfl_u(s.cg.x, src);
-    s.cg.y = shfl_u(s.cg.y, src);
-    s.tg.x = shfl_u(s.tg.x, src);
-    s.tg.y = shfl_u(s.tg.y, src);
-    s.oct = shfl_u(s.oct, src);
-    s.stack_size = shfl_i(s.stack_size, src);
-    s.tlas_ss = shfl_i(s.tlas_ss, src);
-    s.NodeOffset = shfl_i(s.NodeOffset, src);
-    s.TriOffset = shfl_i(s.TriOffset, src);
-    s.MatOffset = shfl_i(s.MatOffset, src);
-    s.Reps = shfl_i(s.Reps, src);
-    s.ray_index = shfl_u(s.ray_index, src);
-    s.scol = shfl_u(s.scol, src);
-    s.gcol = shfl_u(s.gcol, src);
-    s.active = has;
 }
 
 // The drain loop of the any-hit kernel for groups of G lanes (tt_wide.h's wide_phase with the
@@ -171,24 +115,15 @@ __device__ void shadow_wide_phase(const ShadowArgs& A, ShadowWide& st, uint2 (*s
                     exhaust(st);
                 }
             } else if (st.cg.y & 0xff000000u) {  // :374-403
-                const uint32_t cio = firstbithigh(st.cg.y);
-                const uint32_t slot = (cio - 24u) ^ (st.oct & 0xffu);
-                const uint32_t rel = __builtin_popcount(st.cg.y & ~(0xffffffffu << slot));
-                const uint32_t child = st.cg.x + rel;
-                st.cg.y &= ~(1u << cio);
+                const uint32_t child = take_child(st.cg, st.oct);
                 bool ok = true;
                 if (st.cg.y & 0xff000000u) TT_PUSH(st.cg, ok);
                 if (ok) {
-                    const uint32_t no = node_offset(child);
-                    const uint4 n0 = buffer_load16(nodes, no), n1 = buffer_load16(nodes, no + 16u),
-                                n2 = buffer_load16(nodes, no + 32u), n3 = buffer_load16(nodes, no + 48u),
-                                n4 = buffer_load16(nodes, no + 64u);
-                    const uint32_t hitmask =
-                        group_or<G>(node_intersect_part<G>(n0, n1, n2, n3, n4, st.ray, st.oct, st.max_distance, sub));
-                    st.cg.y = (hitmask & 0xff000000u) | (n0.w >> 24);
-                    st.tg.y = hitmask & 0x00ffffffu;
-                    st.cg.x = n1.x + (uint32_t)st.NodeOffset;
-                    st.tg.x = n1.y + (uint32_t)st.TriOffset;
+                    const NodeWords n = load_node<0>(nodes, child);
+                    const uint32_t hitmask = group_or<G>(
+                        node_intersect_part<G>(n.n0, n.n1, n.n2, n.n3, n.n4, st.ray, st.oct, st.max_distance, sub));
+                    st.cg = node_group(hitmask, n, st.NodeOffset);
+                    st.tg = tri_group(hitmask, n, st.TriOffset);
                     st.Reps++;
                     if (STATS && sub == 0u) C.nodes++;
                 } else {
@@ -205,31 +140,16 @@ __device__ void shadow_wide_phase(const ShadowArgs& A, ShadowWide& st, uint2 (*s
             if (st.active && st.tg.y != 0u && st.tlas_ss == -1) {  // :411-435 TLAS leaf -> BLAS
                 const uint32_t mo = firstbithigh(st.tg.y);
                 st.tg.y &= ~(1u << mo);
-                const float4* mp = reinterpret_cast<const float4*>(A.leaf + (st.tg.x + mo));  // LeafMesh
-                const float4 m0 = mp[0], m1 = mp[1], m2 = mp[2];
-                const int4 mo4 = reinterpret_cast<const int4*>(mp)[3];
-                st.NodeOffset = mo4.y;
-                st.TriOffset = mo4.x;
+                const LeafEntry e = load_leaf_mesh<false>(A.leaf, st.tg.x + mo);
+                st.NodeOffset = e.off.y;
+                st.TriOffset = e.off.x;
                 bool ok = true;
                 if (st.tg.y != 0u) TT_PUSH(st.tg, ok);
                 if (ok && (st.cg.y & 0xff000000u)) TT_PUSH(st.cg, ok);
                 if (ok) {
                     st.tlas_ss = stack_size;
-                    st.MatOffset = mo4.z;
-                    const LaneRay& ray = st.ray;
-                    LaneRay nr;
-                    nr.dx = fma_(m0.z, ray.dz, fma_(m0.y, ray.dy, m0.x * ray.dx));
-                    nr.dy = fma_(m1.z, ray.dz, fma_(m1.y, ray.dy, m1.x * ray.dx));
-                    nr.dz = fma_(m2.z, ray.dz, fma_(m2.y, ray.dy, m2.x * ray.dx));
-                    nr.ox = fma_(m0.z, ray.oz, fma_(m0.y, ray.oy, m0.x * ray.ox)) + m0.w;
-                    nr.oy = fma_(m1.z, ray.oz, fma_(m1.y, ray.oy, m1.x * ray.ox)) + m1.w;
-                    nr.oz = fma_(m2.z, ray.oz, fma_(m2.y, ray.oy, m2.x * ray.ox)) + m2.w;
-                    nr.ix = rcp_rn(nr.dx);
-                    nr.iy = rcp_rn(nr.dy);
-                    nr.iz = rcp_rn(nr.dz);
-                    st.ray = nr;
-                    st.oct = octant_inv4(st.ray);
-                    st.cg = make_uint2((uint32_t)mo4.w, 0x80000000u);
+                    st.MatOffset = e.off.z;
+                    enter_object_space(e, st.ray, st.oct, st.cg);
                     if (STATS && sub == 0u) C.blas++;
                 } else {
                     st.active = false;
@@ -285,11 +205,7 @@ __device__ void shadow_wide_phase(const ShadowArgs& A, ShadowWide& st, uint2 (*s
         if (st.active && st.tg.y == 0u && (st.cg.y & 0xff000000u) == 0u) {
             if (stack_size != 0) {
                 if (stack_size == st.tlas_ss) {
-                    st.NodeOffset = (int32_t)A.tlas_base;
-                    st.TriOffset = 0;
-                    st.tlas_ss = -1;
-                    st.ray = st.wray;
-                    st.oct = octant_inv4(st.ray);
+                    leave_blas(A.tlas_base, st.wray, st.NodeOffset, st.TriOffset, st.tlas_ss, st.ray, st.oct);
                 }
                 TT_POP(st.cg);
             } else {
@@ -381,8 +297,9 @@ __device__ __forceinline__ void shadow_body(const ShadowArgs& A) {
 #if TT_WIDE
         // the queue is dry and the live rays fit in 2-lane groups: cooperative drain (tt_wide.h)
         if (pool_dry && TT_WAVE - n_idle <= TT_WIDE_ENTER) {
-            ShadowWide st{ray, wray, max_distance, thr, cg, tg, oct, stack_size, tlas_ss, NodeOffset, TriOffset,
-                          MatOffset, Reps, ray_index, tid, gtid, (int32_t)tg.y >= 0};
+            ShadowWide st{{ray, wray, cg, tg, oct, stack_size, tlas_ss, NodeOffset, TriOffset, MatOffset, Reps,
+                           ray_index, tid, gtid, (int32_t)tg.y >= 0},
+                          max_distance, thr};
             regroup_shadow<2>(st, __ballot((int32_t)tg.y >= 0), lane);
             auto occ_w = [&](const ShadowWide& w) { do_occlude(w.ray_index); };
             auto reach_w = [&](const ShadowWide& w) { do_reach(w.ray_index, w.wray, w.thr); };
@@ -400,18 +317,11 @@ __device__ __forceinline__ void shadow_body(const ShadowArgs& A) {
                 new_count = sched_reserve(A.ctl, n_rays, n_tiles, lane, n_idle - avail, wave_id, S, new_base);
                 more = new_count > 0 ? 1u : 0u;
             }
-            const uint32_t take_old = min(avail, n_idle);
-            const uint32_t take_new = min(n_idle - take_old, new_count);
-            const uint32_t rank = lane_prefix(idle);
-            uint32_t widx = 0xffffffffu;
-            if (rank < take_old) widx = pool_next + rank;
-            else if (rank - take_old < take_new) widx = new_base + (rank - take_old);
-            if (new_count > 0) {
-                pool_next = new_base + take_new;
-                pool_end = new_base + new_count;
-            } else {
-                pool_next += take_old;
-            }
+            const PoolTake pt = pool_take<false>(idle, n_idle, new_base, new_count, pool_next, pool_end, more);
+            const uint32_t widx = pt.widx;
+            pool_next = pt.pool_next;
+            pool_end = pt.pool_end;
+            more = pt.more;
             if ((int32_t)tg.y < 0 && widx != 0xffffffffu) {  // :355-371
                 ray_index = widx;
                 const uint4* rp = reinterpret_cast<const uint4*>(A.rays + ray_index);
@@ -451,23 +361,14 @@ __device__ __forceinline__ void shadow_body(const ShadowArgs& A) {
                 if (STATS) c_reps++;
                 do_exhaust(ray_index);
             } else if (cg.y & 0xff000000u) {  // :374-403
-                const uint32_t cio = firstbithigh(cg.y);
-                const uint32_t slot = (cio - 24u) ^ (oct & 0xffu);
-                const uint32_t rel = __builtin_popcount(cg.y & ~(0xffffffffu << slot));
-                const uint32_t child = cg.x + rel;
-                cg.y &= ~(1u << cio);
+                const uint32_t child = take_child(cg, oct);
                 bool ok = true;
                 if (cg.y & 0xff000000u) TT_PUSH(cg, ok);
                 if (ok) {
-                    const uint32_t no = node_offset(child);
-                    const uint4 n0 = buffer_load16(nodes, no), n1 = buffer_load16(nodes, no + 16u),
-                                n2 = buffer_load16(nodes, no + 32u), n3 = buffer_load16(nodes, no + 48u),
-                                n4 = buffer_load16(nodes, no + 64u);
-                    const uint32_t hitmask = node_intersect(n0, n1, n2, n3, n4, ray, oct, max_distance);
-                    cg.y = (hitmask & 0xff000000u) | (n0.w >> 24);
-                    tg.y = hitmask & 0x00ffffffu;
-                    cg.x = n1.x + (uint32_t)NodeOffset;
-                    tg.x = n1.y + (uint32_t)TriOffset;
+                    const NodeWords n = load_node<0>(nodes, child);
+                    const uint32_t hitmask = node_intersect(n.n0, n.n1, n.n2, n.n3, n.n4, ray, oct, max_distance);
+                    cg = node_group(hitmask, n, NodeOffset);
+                    tg = tri_group(hitmask, n, TriOffset);
                     Reps++;
                     if (STATS) c_nodes++;
                 } else {
@@ -482,31 +383,17 @@ __device__ __forceinline__ void shadow_body(const ShadowArgs& A) {
             if ((int32_t)tg.y > 0 && tlas_ss == -1) {  // :411-435 TLAS leaf -> BLAS
                 const uint32_t mo = firstbithigh(tg.y);
                 tg.y &= ~(1u << mo);
-                const float4* mp = reinterpret_cast<const float4*>(A.leaf + (tg.x + mo));  // LeafMesh
-                const float4 m0 = mp[0], m1 = mp[1], m2 = mp[2];
-                const int4 mo4 = reinterpret_cast<const int4*>(mp)[3];
-                NodeOffset = mo4.y;
-                TriOffset = mo4.x;
+                const LeafEntry e = load_leaf_mesh<false>(A.leaf, tg.x + mo);
+                NodeOffset = e.off.y;
+                TriOffset = e.off.x;
                 bool ok = true;
                 if (tg.y != 0u) TT_PUSH(tg, ok);
                 if (ok && (cg.y & 0xff000000u)) TT_PUSH(cg, ok);
                 tg.y = 0u;
                 if (ok) {
                     tlas_ss = stack_size;
-                    MatOffset = mo4.z;
-                    LaneRay nr;
-                    nr.dx = fma_(m0.z, ray.dz, fma_(m0.y, ray.dy, m0.x * ray.dx));
-                    nr.dy = fma_(m1.z, ray.dz, fma_(m1.y, ray.dy, m1.x * ray.dx));
-                    nr.dz = fma_(m2.z, ray.dz, fma_(m2.y, ray.dy, m2.x * ray.dx));
-                    nr.ox = fma_(m0.z, ray.oz, fma_(m0.y, ray.oy, m0.x * ray.ox)) + m0.w;
-                    nr.oy = fma_(m1.z, ray.oz, fma_(m1.y, ray.oy, m1.x * ray.ox)) + m1.w;
-                    nr.oz = fma_(m2.z, ray.oz, fma_(m2.y, ray.oy, m2.x * ray.ox)) + m2.w;
-                    nr.ix = rcp_rn(nr.dx);
-                    nr.iy = rcp_rn(nr.dy);
-                    nr.iz = rcp_rn(nr.dz);
-                    ray = nr;
-                    oct = octant_inv4(ray);
-                    cg = make_uint2((uint32_t)mo4.w, 0x80000000u);
+                    MatOffset = e.off.z;
+                    enter_object_space(e, ray, oct, cg);
                     if (STATS) c_blas++;
                 } else {
                     tg.y = TT_IDLE;
@@ -534,11 +421,7 @@ __device__ __forceinline__ void shadow_body(const ShadowArgs& A) {
         if (tg.y == 0u && (cg.y & 0xff000000u) == 0u) {
             if (stack_size != 0) {
                 if (stack_size == tlas_ss) {
-                    NodeOffset = (int32_t)A.tlas_base;
-                    TriOffset = 0;
-                    tlas_ss = -1;
-                    ray = wray;
-                    oct = octant_inv4(ray);
+                    leave_blas(A.tlas_base, wray, NodeOffset, TriOffset, tlas_ss, ray, oct);
                 }
                 TT_POP(cg);
             } else {  // reached the light (TerrainExists false): :457-485
@@ -654,17 +537,10 @@ hipError_t tt_launch_shadow(const ShadowArgs* a, uint32_t grid, hipStream_t st, 
     return matcheck ? launch_shadow<false, true>(*a, grid, st) : launch_shadow<false, false>(*a, grid, st);
 }
 
-template <bool S, bool M>
-static int shadow_occ() {
-    int b = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, tt_shadow_kernel<S, M>, TT_BLOCK, 0) != hipSuccess) b = 1;
-    return b;
-}
-
 // resident blocks per CU per instantiation, index stats * 2 + matcheck
 void tt_shadow_occupancy_table(int* out4) {
-    out4[0] = shadow_occ<false, false>();
-    out4[1] = shadow_occ<false, true>();
-    out4[2] = shadow_occ<true, false>();
-    out4[3] = shadow_occ<true, true>();
+    out4[0] = occupancy_of(tt_shadow_kernel<false, false>);
+    out4[1] = occupancy_of(tt_shadow_kernel<false, true>);
+    out4[2] = occupancy_of(tt_shadow_kernel<true, false>);
+    out4[3] = occupancy_of(tt_shadow_kernel<true, true>);
 }

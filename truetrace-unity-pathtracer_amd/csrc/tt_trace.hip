@@ -183,17 +183,8 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     static_assert(!LEAF || (!STATS && !MATCHECK && !ORD), "the leaf-TLAS form has no stats / material / order variants");
     __shared__ uint2 s_stack[TT_LDS_STACK][TT_BLOCK];
     // (read before the kernel's first store, so the compiler can prove the loads unclobbered and make them scalar)
-    float4 L0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), L1 = L0, L2 = L0;  // LEAF: W2L rows of the one instance
-    int4 L4 = make_int4(0, 0, 0, 0);                                     // TriOffset, NodeOffset, MatOffset, BLAS root
-    int32_t L_mesh = 0;                                                  // mesh id
-    if (LEAF) {
-        const float4* mp = reinterpret_cast<const float4*>(A.leaf + (A.root.base_tri + firstbithigh(A.root.bits)));
-        L0 = mp[0];
-        L1 = mp[1];
-        L2 = mp[2];
-        L4 = reinterpret_cast<const int4*>(mp)[3];
-        L_mesh = reinterpret_cast<const int4*>(mp)[4].x;
-    }
+    LeafEntry L{};  // LEAF: the LeafMesh record of the one instance
+    if (LEAF) L = load_leaf_mesh<true>(A.leaf, A.root.base_tri + firstbithigh(A.root.bits));
     const uint32_t tid = threadIdx.x;
     zero_next_control(A.ctl_next, tid);
     const uint32_t gtid = blockIdx.x * TT_BLOCK + tid;
@@ -238,10 +229,10 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     int32_t stack_size = 0, tlas_ss = -1;
     int32_t NodeOffset = 0, TriOffset = 0, MatOffset = 0, mesh_id = -1, Reps = 0;
     if (LEAF) {  // wave-uniform for the whole launch
-        NodeOffset = L4.y;
-        TriOffset = L4.x;
-        MatOffset = L4.z;
-        mesh_id = L_mesh;
+        NodeOffset = L.off.y;
+        TriOffset = L.off.x;
+        MatOffset = L.off.z;
+        mesh_id = L.mesh_id;
     }
     uint32_t c_nodes = 0, c_tris = 0, c_blas = 0, c_acc = 0, c_rays = 0, c_hits = 0, c_reps = 0, c_ovf = 0;
     uint32_t d_iter = 0, d_node_lanes = 0, d_node_iters = 0, d_tri_lanes = 0, d_tri_iters = 0, d_active_lanes = 0;
@@ -257,33 +248,18 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
             TT_DB(8);
             const uint32_t mo = firstbithigh(tg.y);
             tg.y &= ~(1u << mo);
-            const float4* mp = reinterpret_cast<const float4*>(A.leaf + (tg.x + mo));  // LeafMesh
-            const float4 m0 = mp[0], m1 = mp[1], m2 = mp[2];
-            const int4 mo4 = reinterpret_cast<const int4*>(mp)[3];
-            const int4 mo5 = reinterpret_cast<const int4*>(mp)[4];
-            mesh_id = mo5.x;
-            NodeOffset = mo4.y;
-            TriOffset = mo4.x;
+            const LeafEntry e = load_leaf_mesh<true>(A.leaf, tg.x + mo);
+            mesh_id = e.mesh_id;
+            NodeOffset = e.off.y;
+            TriOffset = e.off.x;
             bool ok = true;
             if (tg.y != 0u) TT_PUSH(tg, ok);
             if (ok && (cg.y & 0xff000000u)) TT_PUSH(cg, ok);
             tg.y = 0u;
             if (ok) {
                 tlas_ss = stack_size;
-                MatOffset = mo4.z;
-                LaneRay nr;
-                nr.dx = fma_(m0.z, ray.dz, fma_(m0.y, ray.dy, m0.x * ray.dx));
-                nr.dy = fma_(m1.z, ray.dz, fma_(m1.y, ray.dy, m1.x * ray.dx));
-                nr.dz = fma_(m2.z, ray.dz, fma_(m2.y, ray.dy, m2.x * ray.dx));
-                nr.ox = fma_(m0.z, ray.oz, fma_(m0.y, ray.oy, m0.x * ray.ox)) + m0.w;
-                nr.oy = fma_(m1.z, ray.oz, fma_(m1.y, ray.oy, m1.x * ray.ox)) + m1.w;
-                nr.oz = fma_(m2.z, ray.oz, fma_(m2.y, ray.oy, m2.x * ray.ox)) + m2.w;
-                nr.ix = rcp_rn(nr.dx);
-                nr.iy = rcp_rn(nr.dy);
-                nr.iz = rcp_rn(nr.dz);
-                ray = nr;
-                oct = octant_inv4(ray);
-                cg = make_uint2((uint32_t)mo4.w, 0x80000000u);
+                MatOffset = e.off.z;
+                enter_object_space(e, ray, oct, cg);
                 if (STATS) c_blas++;
             } else {
                 tg.y = TT_IDLE;
@@ -327,8 +303,9 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
 #if TT_WIDE
         if (to_wide) {
             TT_DB(13);
-            WideState st{ray, world_ray(), best, cg, tg, oct, stack_size, tlas_ss, NodeOffset, TriOffset, MatOffset,
-                         mesh_id, Reps, ray_index, pix, col_w, tid, gtid, (int32_t)tg.y >= 0};
+            WideState st{{ray, world_ray(), cg, tg, oct, stack_size, tlas_ss, NodeOffset, TriOffset, MatOffset, Reps,
+                          ray_index, tid, gtid, (int32_t)tg.y >= 0},
+                         best, mesh_id, pix, col_w};
             regroup<2, LEAF>(st, __ballot((int32_t)tg.y >= 0), lane);
             auto finish_wide = [&](const WideState& w) {
                 const bool hit = write_record<INFO, LEAF>(A, w.ray_index, w.pix, w.col_w, w.best, w.wray, mesh_id, TriOffset);
@@ -365,23 +342,11 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                 if (ORD && A.order && new_count > 0)
                     new_base = (__builtin_amdgcn_readfirstlane(A.order[new_base >> 6]) << 6) | (new_base & 63u);
             }
-            const uint32_t take_old = min(avail, n_idle);
-            const uint32_t take_new = min(n_idle - take_old, new_count);
-            const uint32_t rank = lane_prefix(idle);
-            uint32_t widx = 0xffffffffu;
-            if (rank < take_old) widx = pool_next + rank;
-            else if (rank - take_old < take_new) widx = new_base + (rank - take_old);
-            if (new_count > 0) {  // the old pool was fully consumed (avail < n_idle)
-                pool_next = new_base + take_new;
-                pool_end = new_base + new_count;
-            } else {
-                pool_next += take_old;
-            }
-#if TT_UNIFORM_POOL  // keep the wave-uniform scheduler state in SGPRs (the loop head's tests become SALU)
-            pool_next = __builtin_amdgcn_readfirstlane(pool_next);
-            pool_end = __builtin_amdgcn_readfirstlane(pool_end);
-            more = __builtin_amdgcn_readfirstlane(more);
-#endif
+            const PoolTake pt = pool_take<TT_UNIFORM_POOL != 0>(idle, n_idle, new_base, new_count, pool_next, pool_end, more);
+            const uint32_t widx = pt.widx;
+            pool_next = pt.pool_next;
+            pool_end = pt.pool_end;
+            more = pt.more;
             if ((int32_t)tg.y < 0 && widx != 0xffffffffu) {
                 TT_DB(4);
                 TT_DL(19, true);
@@ -420,21 +385,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                     // push), a miss leaves an empty group: the advance below finishes the ray with the miss record
                     cg = make_uint2(0u, 0u);
                     Reps = 1;
-                    if (root_leaf_hit(A.root, ray, best.t)) {
-                        LaneRay nr;
-                        nr.dx = fma_(L0.z, ray.dz, fma_(L0.y, ray.dy, L0.x * ray.dx));
-                        nr.dy = fma_(L1.z, ray.dz, fma_(L1.y, ray.dy, L1.x * ray.dx));
-                        nr.dz = fma_(L2.z, ray.dz, fma_(L2.y, ray.dy, L2.x * ray.dx));
-                        nr.ox = fma_(L0.z, ray.oz, fma_(L0.y, ray.oy, L0.x * ray.ox)) + L0.w;
-                        nr.oy = fma_(L1.z, ray.oz, fma_(L1.y, ray.oy, L1.x * ray.ox)) + L1.w;
-                        nr.oz = fma_(L2.z, ray.oz, fma_(L2.y, ray.oy, L2.x * ray.ox)) + L2.w;
-                        nr.ix = rcp_rn(nr.dx);
-                        nr.iy = rcp_rn(nr.dy);
-                        nr.iz = rcp_rn(nr.dz);
-                        ray = nr;
-                        oct = octant_inv4(ray);
-                        cg = make_uint2((uint32_t)L4.w, 0x80000000u);
-                    }
+                    if (root_leaf_hit(A.root, ray, best.t)) enter_object_space(L, ray, oct, cg);
                 }
                 if (!LEAF) {
                     wray = ray;
@@ -466,6 +417,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
         }
 
         // ------------------------------------------------------------- node phase
+        // valu_mix:node:begin
         if (STATS) {  // SIMD-efficiency diagnostics (wave-uniform; lane 0 accumulates)
             const uint64_t nm = __ballot(tg.y == 0u && Reps < TT_MAX_REPS && (cg.y & 0xff000000u));
             const uint64_t am = __ballot((int32_t)tg.y >= 0);  // outside the lane-0 branch: a ballot there sees lane 0 only
@@ -485,11 +437,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                 keep_record(A, ray_index);
                 if (ORD) record_chunk_cost(A, swizzle, ray_index, Reps);
             } else if (cg.y & 0xff000000u) {  // IntersectionKernels.compute:157-187
-                const uint32_t cio = firstbithigh(cg.y);
-                const uint32_t slot = (cio - 24u) ^ (oct & 0xffu);
-                const uint32_t rel = __builtin_popcount(cg.y & ~(0xffffffffu << slot));
-                const uint32_t child = cg.x + rel;
-                cg.y &= ~(1u << cio);
+                const uint32_t child = take_child(cg, oct);
                 bool ok = true;
                 if (cg.y & 0xff000000u) {
                     TT_DB(7);
@@ -504,16 +452,10 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                         d_lead_same += child == lead ? 1u : 0u;
                         d_uniform += (same == all && lane == (uint32_t)__builtin_ctzll(all)) ? 1u : 0u;
                     }
-                    const uint32_t no = node_offset(child);
-                    const uint4 n0 = buffer_load16<TT_NODE_CPOL>(nodes, no), n1 = buffer_load16<TT_NODE_CPOL>(nodes, no + 16u),
-                                n2 = buffer_load16<TT_NODE_CPOL>(nodes, no + 32u),
-                                n3 = buffer_load16<TT_NODE_CPOL>(nodes, no + 48u),
-                                n4 = buffer_load16<TT_NODE_CPOL>(nodes, no + 64u);
-                    const uint32_t hitmask = node_intersect(n0, n1, n2, n3, n4, ray, oct, best.t);
-                    cg.y = (hitmask & 0xff000000u) | (n0.w >> 24);
-                    tg.y = hitmask & 0x00ffffffu;
-                    cg.x = n1.x + (uint32_t)NodeOffset;
-                    tg.x = n1.y + (uint32_t)TriOffset;
+                    const NodeWords n = load_node<TT_NODE_CPOL>(nodes, child);
+                    const uint32_t hitmask = node_intersect(n.n0, n.n1, n.n2, n.n3, n.n4, ray, oct, best.t);
+                    cg = node_group(hitmask, n, NodeOffset);
+                    tg = tri_group(hitmask, n, TriOffset);
                     Reps++;
                     if (STATS) c_nodes++;
                 } else {
@@ -528,6 +470,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
             }
             if (!LEAF && (int32_t)tg.y > 0 && tlas_ss == -1) enter_blas();  // :194-219 TLAS leaf -> BLAS
         }
+        // valu_mix:node:end
 
         if (STATS) {
             const uint64_t tm = __ballot((int32_t)tg.y > 0);
@@ -537,6 +480,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
             }
         }
         // --------------------------------------------------------- triangle phase
+        // valu_mix:tri:begin
         if ((int32_t)tg.y > 0) {  // :220-226, highest bit first, one triangle per pass
             TT_DB(9);
             TT_DL(18, true);
@@ -549,6 +493,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                 c_acc += acc ? 1u : 0u;
             }
         }
+        // valu_mix:tri:end
 
         // ----------------------------------------- advance: pop / finish (:228-251)
         // One place for every lane whose group is used up, whether it came from a node step or
@@ -559,11 +504,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                 TT_DB(11);
                 if (!LEAF && stack_size == tlas_ss) {
                     TT_DB(12);
-                    NodeOffset = (int32_t)A.tlas_base;
-                    TriOffset = 0;
-                    tlas_ss = -1;
-                    ray = world_ray();
-                    oct = octant_inv4(ray);
+                    leave_blas(A.tlas_base, world_ray(), NodeOffset, TriOffset, tlas_ss, ray, oct);
                 }
                 TT_POP(cg);
             } else {
@@ -680,55 +621,34 @@ hipError_t tt_launch_trace(const TraceArgs& a, bool stats, bool matcheck, int in
     return matcheck ? launch_info<false, true>(a, info, false, grid, st) : launch_info<false, false>(a, info, leaf, grid, st);
 }
 
-// Occupancy (resident blocks per CU) of every instantiation: they differ in registers, so each
-// launch sizes its persistent grid from its own entry.
-template <bool S, bool M, int I>
-static int occ_one() {
-    int b = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, tt_trace_kernel<S, M, I>, TT_BLOCK, 0) != hipSuccess) b = 1;
-    return b;
-}
-template <bool M, int I>
-static int occ_ord() {
-    int b = 0;
-    const hipError_t e = M ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, tt_trace_kernel_ord_mat<I>, TT_BLOCK, 0)
-                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, tt_trace_kernel_ord<I>, TT_BLOCK, 0);
-    return e == hipSuccess ? b : 1;
-}
-template <bool IND, int I>
-static int occ_leaf() {
-    int b = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, tt_trace_leaf_kernel<IND, I>, TT_BLOCK, 0) == hipSuccess ? b : 1;
-}
+// Occupancy (resident blocks per CU) of every instantiation (occupancy_of, tt_traverse.h).
 // index = stats*6 + matcheck*3 + info; 12 + matcheck*3 + info: the adaptive-order kernels;
 // 18 + indirect*3 + info: the leaf-TLAS kernels
 hipError_t tt_trace_occupancy_table(int* out24) {
-    int* out18 = out24;
-    int* out12 = out18;
-    out12[0] = occ_one<false, false, 0>();
-    out12[1] = occ_one<false, false, 1>();
-    out12[2] = occ_one<false, false, 2>();
-    out12[3] = occ_one<false, true, 0>();
-    out12[4] = occ_one<false, true, 1>();
-    out12[5] = occ_one<false, true, 2>();
-    out12[6] = occ_one<true, false, 0>();
-    out12[7] = occ_one<true, false, 1>();
-    out12[8] = occ_one<true, false, 2>();
-    out12[9] = occ_one<true, true, 0>();
-    out12[10] = occ_one<true, true, 1>();
-    out12[11] = occ_one<true, true, 2>();
-    out18[12] = occ_ord<false, 0>();
-    out18[13] = occ_ord<false, 1>();
-    out18[14] = occ_ord<false, 2>();
-    out18[15] = occ_ord<true, 0>();
-    out18[16] = occ_ord<true, 1>();
-    out18[17] = occ_ord<true, 2>();
-    out24[18] = occ_leaf<false, 0>();
-    out24[19] = occ_leaf<false, 1>();
-    out24[20] = occ_leaf<false, 2>();
-    out24[21] = occ_leaf<true, 0>();
-    out24[22] = occ_leaf<true, 1>();
-    out24[23] = occ_leaf<true, 2>();
+    out24[0] = occupancy_of(tt_trace_kernel<false, false, 0>);
+    out24[1] = occupancy_of(tt_trace_kernel<false, false, 1>);
+    out24[2] = occupancy_of(tt_trace_kernel<false, false, 2>);
+    out24[3] = occupancy_of(tt_trace_kernel<false, true, 0>);
+    out24[4] = occupancy_of(tt_trace_kernel<false, true, 1>);
+    out24[5] = occupancy_of(tt_trace_kernel<false, true, 2>);
+    out24[6] = occupancy_of(tt_trace_kernel<true, false, 0>);
+    out24[7] = occupancy_of(tt_trace_kernel<true, false, 1>);
+    out24[8] = occupancy_of(tt_trace_kernel<true, false, 2>);
+    out24[9] = occupancy_of(tt_trace_kernel<true, true, 0>);
+    out24[10] = occupancy_of(tt_trace_kernel<true, true, 1>);
+    out24[11] = occupancy_of(tt_trace_kernel<true, true, 2>);
+    out24[12] = occupancy_of(tt_trace_kernel_ord<0>);
+    out24[13] = occupancy_of(tt_trace_kernel_ord<1>);
+    out24[14] = occupancy_of(tt_trace_kernel_ord<2>);
+    out24[15] = occupancy_of(tt_trace_kernel_ord_mat<0>);
+    out24[16] = occupancy_of(tt_trace_kernel_ord_mat<1>);
+    out24[17] = occupancy_of(tt_trace_kernel_ord_mat<2>);
+    out24[18] = occupancy_of(tt_trace_leaf_kernel<false, 0>);
+    out24[19] = occupancy_of(tt_trace_leaf_kernel<false, 1>);
+    out24[20] = occupancy_of(tt_trace_leaf_kernel<false, 2>);
+    out24[21] = occupancy_of(tt_trace_leaf_kernel<true, 0>);
+    out24[22] = occupancy_of(tt_trace_leaf_kernel<true, 1>);
+    out24[23] = occupancy_of(tt_trace_leaf_kernel<true, 2>);
     return hipGetLastError();
 }
 

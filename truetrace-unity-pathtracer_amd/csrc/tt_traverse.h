@@ -1,7 +1,8 @@
 // tt_traverse.h — device-side building blocks shared by the closest-hit (tt_trace.hip) and the
 // any-hit (tt_shadow.hip) CWBVH8 traversal kernels: tuning macros, the node test
-// (CommonData.cginc:641-707), the triangle test (IntersectionKernels.compute:14-57), raw-buffer
-// fetch helpers and the per-XCD segment ray scheduler.
+// (CommonData.cginc:641-707), the steps of the traversal loop that the scalar loops and their drains
+// (tt_wide.h) share, the triangle test (IntersectionKernels.compute:14-57), raw-buffer fetch helpers and
+// the per-XCD segment ray scheduler with the refill's pool arithmetic.
 #ifndef TT_TRAVERSE_H
 #define TT_TRAVERSE_H
 #include "tt_device.h"
@@ -133,18 +134,24 @@ __device__ __forceinline__ uint32_t buffer_load4(__amdgpu_buffer_rsrc_t r, uint3
 // derived copy of the node array with every 80-B node at the start of its own 128-B line (tt_scene_api.hip
 // keeps it in step with the reference array), so a node visit touches one cache line instead of 1.5.
 static_assert(TT_NODE_STRIDE == 80 || TT_NODE_STRIDE == 128, "node stride: 80 (the reference array) or 128");
+// valu_mix:node:begin  (tools/valu_mix.py counts the instructions of the lines between a begin / end pair as the
+// node step, or with `tri` the triangle pass, of the closest-hit loop; pairs may repeat)
 __device__ __forceinline__ uint32_t node_offset(uint32_t i) {
     if (TT_NODE_STRIDE == 128) return i << 7;
     uint32_t r;
     asm("v_lshl_add_u32 %0, %1, 2, %1\n\tv_lshlrev_b32 %0, 4, %0" : "=&v"(r) : "v"(i));
     return r;
 }
+// valu_mix:node:end
+// valu_mix:tri:begin
 __device__ __forceinline__ uint32_t tri_offset(uint32_t i) {
     uint32_t r;
     asm("v_lshl_add_u32 %0, %1, 1, %1\n\tv_lshlrev_b32 %0, 4, %0" : "=&v"(r) : "v"(i));
     return r;
 }
+// valu_mix:tri:end
 
+// valu_mix:node:begin
 // cwbvh_node_intersect — CommonData.cginc:641-707
 __device__ __forceinline__ uint32_t node_intersect(const uint4 n0, const uint4 n1, const uint4 n2,
                                                    const uint4 n3, const uint4 n4, const LaneRay& r,
@@ -217,6 +224,92 @@ __device__ __forceinline__ uint32_t node_intersect(const uint4 n0, const uint4 n
     return hit_mask;
 }
 
+// ------------------------------------------------------------------ traversal steps
+// The steps of the reference's loop (IntersectionKernels.compute:157-251; the any-hit loop :374-494 takes the same
+// ones) that the four loops -- trace_body, wide_phase, shadow_body, shadow_wide_phase -- share. They take and
+// return values or references to the caller's own variables; the stack (TT_PUSH / TT_POP below) stays a macro.
+
+// :157-165 the next child of the node group cg in the ray's octant order: its node index; its bit is cleared
+__device__ __forceinline__ uint32_t take_child(uint2& cg, uint32_t oct) {
+    const uint32_t cio = firstbithigh(cg.y);
+    const uint32_t slot = (cio - 24u) ^ (oct & 0xffu);
+    const uint32_t rel = __builtin_popcount(cg.y & ~(0xffffffffu << slot));
+    const uint32_t child = cg.x + rel;
+    cg.y &= ~(1u << cio);
+    return child;
+}
+// The 80 B of one node: five 16-B loads. CPOL: TT_NODE_CPOL in the scalar closest-hit loop, 0 in its drain and
+// in both any-hit loops.
+struct NodeWords {
+    uint4 n0, n1, n2, n3, n4;
+};
+template <int CPOL>
+__device__ __forceinline__ NodeWords load_node(__amdgpu_buffer_rsrc_t nodes, uint32_t child) {
+    const uint32_t no = node_offset(child);
+    return NodeWords{buffer_load16<CPOL>(nodes, no), buffer_load16<CPOL>(nodes, no + 16u),
+                     buffer_load16<CPOL>(nodes, no + 32u), buffer_load16<CPOL>(nodes, no + 48u),
+                     buffer_load16<CPOL>(nodes, no + 64u)};
+}
+// :170-187 a node's hit mask folded into the two groups at the ray's level: the node group (child base; hit
+// inner children | imask) and the triangle group (triangle base; hit leaf bits). Returned by value: one function
+// writing cg / tg through references made the compiler lay the loops' branches out differently.
+__device__ __forceinline__ uint2 node_group(uint32_t hitmask, const NodeWords& n, int32_t NodeOffset) {
+    return make_uint2(n.n1.x + (uint32_t)NodeOffset, (hitmask & 0xff000000u) | (n.n0.w >> 24));
+}
+__device__ __forceinline__ uint2 tri_group(uint32_t hitmask, const NodeWords& n, int32_t TriOffset) {
+    return make_uint2(n.n1.y + (uint32_t)TriOffset, hitmask & 0x00ffffffu);
+}
+// valu_mix:node:end
+
+// :194-219 the LeafMesh record of a TLAS leaf's instance: the world-to-local rows and the offset words. The mesh
+// id is loaded only where asked (the any-hit loops never read it).
+struct LeafEntry {
+    float4 m0, m1, m2;  // W2L rows
+    int4 off;           // TriOffset, NodeOffset, MatOffset, BLAS root
+    int32_t mesh_id;
+};
+template <bool MESH_ID>
+__device__ __forceinline__ LeafEntry load_leaf_mesh(const LeafMesh* leaf, uint32_t i) {
+    const float4* mp = reinterpret_cast<const float4*>(leaf + i);
+    LeafEntry e;
+    e.m0 = mp[0];
+    e.m1 = mp[1];
+    e.m2 = mp[2];
+    e.off = reinterpret_cast<const int4*>(mp)[3];
+    e.mesh_id = MESH_ID ? reinterpret_cast<const int4*>(mp)[4].x : 0;
+    return e;
+}
+// :207-213 the ray in the instance's object space (3x4 transform, then the reciprocal direction)
+__device__ __forceinline__ LaneRay to_object_space(const float4 m0, const float4 m1, const float4 m2, const LaneRay& ray) {
+    LaneRay nr;
+    nr.dx = fma_(m0.z, ray.dz, fma_(m0.y, ray.dy, m0.x * ray.dx));
+    nr.dy = fma_(m1.z, ray.dz, fma_(m1.y, ray.dy, m1.x * ray.dx));
+    nr.dz = fma_(m2.z, ray.dz, fma_(m2.y, ray.dy, m2.x * ray.dx));
+    nr.ox = fma_(m0.z, ray.oz, fma_(m0.y, ray.oy, m0.x * ray.ox)) + m0.w;
+    nr.oy = fma_(m1.z, ray.oz, fma_(m1.y, ray.oy, m1.x * ray.ox)) + m1.w;
+    nr.oz = fma_(m2.z, ray.oz, fma_(m2.y, ray.oy, m2.x * ray.ox)) + m2.w;
+    nr.ix = rcp_rn(nr.dx);
+    nr.iy = rcp_rn(nr.dy);
+    nr.iz = rcp_rn(nr.dz);
+    return nr;
+}
+// :214-218 the state change of the switch, once the pushes succeeded: the object-space ray, its octant, and the
+// BLAS root as the node group
+__device__ __forceinline__ void enter_object_space(const LeafEntry& e, LaneRay& ray, uint32_t& oct, uint2& cg) {
+    ray = to_object_space(e.m0, e.m1, e.m2, ray);
+    oct = octant_inv4(ray);
+    cg = make_uint2((uint32_t)e.off.w, 0x80000000u);
+}
+// :243-249 BLAS exit in the advance step (the stack is back at the depth of the switch): the TLAS level again
+__device__ __forceinline__ void leave_blas(uint32_t tlas_base, const LaneRay& wray, int32_t& NodeOffset,
+                                           int32_t& TriOffset, int32_t& tlas_ss, LaneRay& ray, uint32_t& oct) {
+    NodeOffset = (int32_t)tlas_base;
+    TriOffset = 0;
+    tlas_ss = -1;
+    ray = wray;
+    oct = octant_inv4(ray);
+}
+
 struct Best {
     float t, u, v;
     int32_t mesh_id, tri_id;
@@ -287,6 +380,7 @@ __device__ __forceinline__ float2 base_uv(const MatView& M, int32_t tri_id, floa
     return make_float2(t0.x * w + t1.x * u + t2.x * v, t0.y * w + t1.y * u + t2.y * v);
 }
 
+// valu_mix:tri:begin
 // One triangle against the ray: `cand` = the reference's geometric accept (u, v range and
 // 0 < t < best_t), `accept` = cand and the material checks passed (the record is taken).
 struct TriCand {
@@ -299,19 +393,53 @@ struct TriData {
     uint4 a, b;
     uint2 c;
 };
-template <bool MATCHECK>
+// CPOL: TT_TRI_CPOL (an A/B knob) in the closest-hit loops; the any-hit loops load with policy 0 whatever it is.
+template <bool MATCHECK, int CPOL = TT_TRI_CPOL>
 __device__ __forceinline__ TriData triangle_load(__amdgpu_buffer_rsrc_t tris, int32_t tri_id) {
     const uint32_t to = tri_offset((uint32_t)tri_id);
     TriData d;
-    d.a = buffer_load16<TT_TRI_CPOL>(tris, to);
-    d.b = buffer_load16<TT_TRI_CPOL>(tris, to + 16u);
+    d.a = buffer_load16<CPOL>(tris, to);
+    d.b = buffer_load16<CPOL>(tris, to + 16u);
     if (MATCHECK) {
-        d.c = buffer_load8<TT_TRI_CPOL>(tris, to + 32u);
+        d.c = buffer_load8<CPOL>(tris, to + 32u);
     } else {
-        d.c.x = buffer_load4<TT_TRI_CPOL>(tris, to + 32u);
+        d.c.x = buffer_load4<CPOL>(tris, to + 32u);
         d.c.y = 0u;
     }
     return d;
+}
+// Moller-Trumbore on pos0 / edges (IntersectionKernels.compute:17-31, CommonData.cginc:596-610), shared by the
+// closest-hit and the any-hit triangle tests: triangle_hit gives t, u, v, TT_IN_TRIANGLE whether (u, v) lies
+// inside the triangle. The t range and the material tests are the callers' (they differ).
+struct TriHit {
+    float t, u, v;
+};
+// IntersectionKernels.compute:29-30: (u >= 0 && u <= 1) && (v >= 0 && u + v <= 1).
+// u <= 1 is implied by v >= 0 && fl(u + v) <= 1 (v >= 0 gives u + v >= u, rounding is monotonic and u
+// is representable; an infinite or NaN u fails u + v <= 1), so it is not evaluated: same predicate.
+// (A macro, like the stack's: as a function, the compiler shapes the branches of the callers' && chains
+// differently from the chain written out.)
+#define TT_IN_TRIANGLE(u, v) (((u) >= 0.0f) && ((v) >= 0.0f && (u) + (v) <= 1.0f))
+__device__ __forceinline__ TriHit triangle_hit(const TriData& d, const LaneRay& r) {
+    const uint4 a = d.a, b = d.b;
+    const float p0x = __uint_as_float(a.x), p0y = __uint_as_float(a.y), p0z = __uint_as_float(a.z);
+    const float e1x = __uint_as_float(a.w), e1y = __uint_as_float(b.x), e1z = __uint_as_float(b.y);
+    const float e2x = __uint_as_float(b.z), e2y = __uint_as_float(b.w), e2z = __uint_as_float(d.c.x);
+    // h = cross(d, e2); a = dot(e1, h)
+    const float hx = fma_(r.dy, e2z, -(r.dz * e2y));
+    const float hy = fma_(r.dz, e2x, -(r.dx * e2z));
+    const float hz = fma_(r.dx, e2y, -(r.dy * e2x));
+    const float aa = fma_(e1z, hz, fma_(e1y, hy, e1x * hx));
+    const float f = rcp_rn(aa);
+    const float sx = r.ox - p0x, sy = r.oy - p0y, sz = r.oz - p0z;
+    const float u = f * fma_(sz, hz, fma_(sy, hy, sx * hx));
+    // q = cross(s, e1)
+    const float qx = fma_(sy, e1z, -(sz * e1y));
+    const float qy = fma_(sz, e1x, -(sx * e1z));
+    const float qz = fma_(sx, e1y, -(sy * e1x));
+    const float v = f * fma_(r.dz, qz, fma_(r.dy, qy, r.dx * qx));
+    const float t = f * fma_(e2z, qz, fma_(e2y, qy, e2x * qx));
+    return TriHit{t, u, v};
 }
 // IgnoreBackfacing (IntersectionKernels.compute:46): dot(normalize(cross(normalize(e1), normalize(e2))),
 // dir) <= 0, normalize(v) = v * (1 / sqrt(dot(v, v))) with the pinned dot / cross.
@@ -330,38 +458,18 @@ __device__ __forceinline__ bool backfacing(float e1x, float e1y, float e1z, floa
 template <bool MATCHECK>
 __device__ __forceinline__ TriCand triangle_test(const TriData& d, const MatView& M, bool bounce0, uint32_t tflags,
                                                  int32_t tri_id, int32_t mat_offset, const LaneRay& r, float best_t) {
-    const uint4 a = d.a, b = d.b;
-    const uint2 c = d.c;
-    const float p0x = __uint_as_float(a.x), p0y = __uint_as_float(a.y), p0z = __uint_as_float(a.z);
-    const float e1x = __uint_as_float(a.w), e1y = __uint_as_float(b.x), e1z = __uint_as_float(b.y);
-    const float e2x = __uint_as_float(b.z), e2y = __uint_as_float(b.w), e2z = __uint_as_float(c.x);
-    // h = cross(d, e2); a = dot(e1, h)
-    const float hx = fma_(r.dy, e2z, -(r.dz * e2y));
-    const float hy = fma_(r.dz, e2x, -(r.dx * e2z));
-    const float hz = fma_(r.dx, e2y, -(r.dy * e2x));
-    const float aa = fma_(e1z, hz, fma_(e1y, hy, e1x * hx));
-    const float f = rcp_rn(aa);
-    const float sx = r.ox - p0x, sy = r.oy - p0y, sz = r.oz - p0z;
-    const float u = f * fma_(sz, hz, fma_(sy, hy, sx * hx));
-    // q = cross(s, e1)
-    const float qx = fma_(sy, e1z, -(sz * e1y));
-    const float qy = fma_(sz, e1x, -(sx * e1z));
-    const float qz = fma_(sx, e1y, -(sy * e1x));
-    const float v = f * fma_(r.dz, qz, fma_(r.dy, qy, r.dx * qx));
-    const float t = f * fma_(e2z, qz, fma_(e2y, qy, e2x * qx));
+    const TriHit h = triangle_hit(d, r);
+    const float t = h.t, u = h.u, v = h.v;
     TriCand R;
     R.t = t;
     R.u = u;
     R.v = v;
-    // IntersectionKernels.compute:29-31: (u >= 0 && u <= 1) && (v >= 0 && u + v <= 1) && (t > 0 && t < best).
-    // u <= 1 is implied by v >= 0 && fl(u + v) <= 1 (v >= 0 gives u + v >= u, rounding is monotonic and u
-    // is representable; an infinite or NaN u fails u + v <= 1), so it is not evaluated: same predicate.
-    R.cand = (u >= 0.0f) && (v >= 0.0f && u + v <= 1.0f) && (t > 0.0f && t < best_t);
+    R.cand = TT_IN_TRIANGLE(u, v) && (t > 0.0f && t < best_t);  // :29-31
     R.accept = R.cand;
     if (MATCHECK && R.accept) {
         // _Materials[MatOffset + MatDat]; an out-of-range StructuredBuffer read returns zeros in
         // D3D (no flags, MatType 0). Cutout alpha test (:35-40), then Invisible at CurBounce == 0 (:48).
-        const uint32_t mi = (uint32_t)(mat_offset + (int32_t)c.y);
+        const uint32_t mi = (uint32_t)(mat_offset + (int32_t)d.c.y);
         const uint32_t w = mi < M.n_mat ? M.word[mi] : 0u;
         if ((w >> TT_MATWORD_CUTOUT) & 1u) {
             const CutoutMat cm = M.cut[mi];
@@ -370,7 +478,8 @@ __device__ __forceinline__ TriCand triangle_test(const TriData& d, const MatView
         const bool glass = (w >> TT_MATWORD_GLASS) & 1u;  // specTrans == 1
         if ((tflags & TT_TRACE_IGNORE_GLASS) && glass) R.accept = false;  // :42-44
         if ((tflags & TT_TRACE_IGNORE_BACKFACING) && bounce0 && !glass && R.accept &&  // :45-47
-            backfacing(e1x, e1y, e1z, e2x, e2y, e2z, r))
+            backfacing(__uint_as_float(d.a.w), __uint_as_float(d.b.x), __uint_as_float(d.b.y), __uint_as_float(d.b.z),
+                       __uint_as_float(d.b.w), __uint_as_float(d.c.x), r))
             R.accept = false;
         if (bounce0 && ((w >> TT_FLAG_INVISIBLE) & 1u)) R.accept = false;
     }
@@ -398,6 +507,7 @@ __device__ __forceinline__ bool intersect_triangle(__amdgpu_buffer_rsrc_t tris, 
     }
     return c.cand;  // counted as an "accept" (candidate passed the t test) before the material check
 }
+// valu_mix:tri:end
 
 // ------------------------------------------------------------------ ray scheduler
 // The work range is cut into TT_SEGS segments of whole 64-ray tiles; blocks start on segment
@@ -447,6 +557,43 @@ __device__ __forceinline__ uint32_t sched_reserve(TraceControl* ctl, uint32_t n_
     return 0u;
 }
 
+__device__ __forceinline__ uint32_t lane_prefix(uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// The refill's pool arithmetic (wave-uniform): the idle lanes take work indices from the wave's pool
+// [pool_next, pool_end) first, then from the new reservation [new_base, new_base + new_count) (sched_reserve's
+// result; 0 rays: none was made or the queue is exhausted), whose rest becomes the pool. Returns this lane's work
+// index (0xffffffff: none) and the pool state after the refill, by value (written through references, the
+// compiler laid the refill's branches out differently). UNIFORM: readfirstlane that state (TT_UNIFORM_POOL; the
+// closest-hit loop only -- the any-hit loop never had it).
+struct PoolTake {
+    uint32_t widx, pool_next, pool_end, more;
+};
+template <bool UNIFORM>
+__device__ __forceinline__ PoolTake pool_take(uint64_t idle, uint32_t n_idle, uint32_t new_base, uint32_t new_count,
+                                              uint32_t pool_next, uint32_t pool_end, uint32_t more) {
+    const uint32_t avail = pool_end - pool_next;
+    const uint32_t take_old = min(avail, n_idle);
+    const uint32_t take_new = min(n_idle - take_old, new_count);
+    const uint32_t rank = lane_prefix(idle);
+    uint32_t widx = 0xffffffffu;
+    if (rank < take_old) widx = pool_next + rank;
+    else if (rank - take_old < take_new) widx = new_base + (rank - take_old);
+    if (new_count > 0) {  // the old pool was fully consumed (avail < n_idle)
+        pool_next = new_base + take_new;
+        pool_end = new_base + new_count;
+    } else {
+        pool_next += take_old;
+    }
+    if (UNIFORM) {  // keep the wave-uniform scheduler state in SGPRs (the loop head's tests become SALU)
+        pool_next = __builtin_amdgcn_readfirstlane(pool_next);
+        pool_end = __builtin_amdgcn_readfirstlane(pool_end);
+        more = __builtin_amdgcn_readfirstlane(more);
+    }
+    return PoolTake{widx, pool_next, pool_end, more};
+}
+
 // Zeroes the next launch's control block (block 0; plain stores, no fence: the kernel boundary
 // orders them before the next launch on the stream).
 __device__ __forceinline__ void zero_next_control(TraceControl* next, uint32_t tid) {
@@ -456,14 +603,18 @@ __device__ __forceinline__ void zero_next_control(TraceControl* next, uint32_t t
     }
 }
 
-__device__ __forceinline__ uint32_t lane_prefix(uint64_t mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, TT_WAVE);
     return v;
+}
+
+// Resident blocks per CU of one kernel instantiation (they differ in registers, so each launch sizes its
+// persistent grid from its own entry of the tables built with this).
+template <class Kernel>
+int occupancy_of(Kernel kernel) {
+    int b = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kernel, TT_BLOCK, 0) == hipSuccess ? b : 1;
 }
 
 }  // namespace

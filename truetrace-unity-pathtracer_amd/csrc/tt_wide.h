@@ -25,17 +25,22 @@ static_assert(TT_WIDE_ENTER >= 1 && TT_WIDE_ENTER <= 32, "TT_WIDE_ENTER must be 
 
 namespace {
 
-// everything a ray carries between steps (IntersectionKernels.compute:62-77 + bookkeeping)
-struct WideState {
+// What a ray of either kernel carries between steps of a drain loop (IntersectionKernels.compute:62-77 +
+// bookkeeping); the closest-hit and the any-hit drain add their own fields (WideState; ShadowWide, tt_shadow.hip).
+struct DrainRay {
     LaneRay ray, wray;
-    Best best;
     uint2 cg, tg;
     uint32_t oct;
-    int32_t stack_size, tlas_ss, NodeOffset, TriOffset, MatOffset, mesh_id, Reps;
-    uint32_t ray_index, pix;
-    float col_w;
+    int32_t stack_size, tlas_ss, NodeOffset, TriOffset, MatOffset, Reps;
+    uint32_t ray_index;
     uint32_t scol, gcol;  // LDS stack column (thread in block) and spill column (grid thread)
     bool active;
+};
+struct WideState : DrainRay {
+    Best best;
+    int32_t mesh_id;
+    uint32_t pix;
+    float col_w;
 };
 
 struct Counters {
@@ -60,13 +65,13 @@ __device__ __forceinline__ void shfl_ray(LaneRay& r, uint32_t src) {
     r.iz = shfl_f(r.iz, src);
 }
 
-// Regroups the rays led by the lanes in `lead` (wave-uniform) into groups of GN consecutive lanes.
-// Must run with every lane of the wave enabled (ds_bpermute reads inactive lanes as zero).
-// LEAF (the leaf-TLAS kernels, tt_trace.hip; 1: the world ray is re-read where needed, 2: it stays resident):
-// tlas_ss, best.mesh_id and, in form 1, wray are not part of a ray's state and the four instance words are
-// wave-uniform, so none of them moves.
-template <int GN, int LEAF = 0>
-__device__ __forceinline__ void regroup(WideState& s, uint64_t lead, uint32_t lane) {
+// The lane whose ray group `lane / GN` takes when the rays led by the lanes in `lead` (wave-uniform) regroup
+// into groups of GN consecutive lanes: the group's rank-th leader (has: there is one; lane 0 stands in if not).
+struct GroupSource {
+    uint32_t lane;
+    bool has;
+};
+__device__ __forceinline__ GroupSource group_source(uint64_t lead, uint32_t lane, uint32_t GN) {
     const uint32_t grp = lane / GN;
     uint32_t src = 0;
     bool has = false;
@@ -79,13 +84,20 @@ __device__ __forceinline__ void regroup(WideState& s, uint64_t lead, uint32_t la
             has = true;
         }
     }
+    return GroupSource{src, has};
+}
+// Regroups the rays led by the lanes in `lead` into groups of GN consecutive lanes: the fields both drains share
+// move here, the callers move their own from the returned source lane.
+// Must run with every lane of the wave enabled (ds_bpermute reads inactive lanes as zero).
+// LEAF (the leaf-TLAS kernels, tt_trace.hip; 1: the world ray is re-read where needed, 2: it stays resident):
+// tlas_ss, best.mesh_id and, in form 1, wray are not part of a ray's state and the four instance words are
+// wave-uniform, so none of them moves.
+template <int GN, int LEAF = 0>
+__device__ __forceinline__ uint32_t regroup_ray(DrainRay& s, uint64_t lead, uint32_t lane) {
+    const GroupSource g = group_source(lead, lane, GN);
+    const uint32_t src = g.lane;
     shfl_ray(s.ray, src);
     if (LEAF != 1) shfl_ray(s.wray, src);
-    s.best.t = shfl_f(s.best.t, src);
-    s.best.u = shfl_f(s.best.u, src);
-    s.best.v = shfl_f(s.best.v, src);
-    if (!LEAF) s.best.mesh_id = shfl_i(s.best.mesh_id, src);
-    s.best.tri_id = shfl_i(s.best.tri_id, src);
     s.cg.x = shfl_u(s.cg.x, src);
     s.cg.y = shfl_u(s.cg.y, src);
     s.tg.x = shfl_u(s.tg.x, src);
@@ -97,15 +109,25 @@ __device__ __forceinline__ void regroup(WideState& s, uint64_t lead, uint32_t la
         s.NodeOffset = shfl_i(s.NodeOffset, src);
         s.TriOffset = shfl_i(s.TriOffset, src);
         s.MatOffset = shfl_i(s.MatOffset, src);
-        s.mesh_id = shfl_i(s.mesh_id, src);
     }
     s.Reps = shfl_i(s.Reps, src);
     s.ray_index = shfl_u(s.ray_index, src);
-    s.pix = shfl_u(s.pix, src);
-    s.col_w = shfl_f(s.col_w, src);
     s.scol = shfl_u(s.scol, src);
     s.gcol = shfl_u(s.gcol, src);
-    s.active = has;
+    s.active = g.has;
+    return src;
+}
+template <int GN, int LEAF = 0>
+__device__ __forceinline__ void regroup(WideState& s, uint64_t lead, uint32_t lane) {
+    const uint32_t src = regroup_ray<GN, LEAF>(s, lead, lane);
+    s.best.t = shfl_f(s.best.t, src);
+    s.best.u = shfl_f(s.best.u, src);
+    s.best.v = shfl_f(s.best.v, src);
+    if (!LEAF) s.best.mesh_id = shfl_i(s.best.mesh_id, src);
+    s.best.tri_id = shfl_i(s.best.tri_id, src);
+    if (!LEAF) s.mesh_id = shfl_i(s.mesh_id, src);
+    s.pix = shfl_u(s.pix, src);
+    s.col_w = shfl_f(s.col_w, src);
 }
 
 // DPP reductions over aligned groups of G lanes (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror)
@@ -214,26 +236,17 @@ __device__ void wide_phase(const TraceArgs& A, WideState& st, uint2 (*s_stack)[T
                 if (STATS && sub == 0u) C.reps++;
                 if (sub == 0u) exhaust(st);
             } else if (st.cg.y & 0xff000000u) {  // IntersectionKernels.compute:157-187
-                const uint32_t cio = firstbithigh(st.cg.y);
-                const uint32_t slot = (cio - 24u) ^ (st.oct & 0xffu);
-                const uint32_t rel = __builtin_popcount(st.cg.y & ~(0xffffffffu << slot));
-                const uint32_t child = st.cg.x + rel;
-                st.cg.y &= ~(1u << cio);
+                const uint32_t child = take_child(st.cg, st.oct);
                 bool ok = true;
                 if (st.cg.y & 0xff000000u) TT_PUSH(st.cg, ok);
                 if (ok) {
                     TT_DB(G == 2 ? 20 : G == 4 ? 21 : 22);
                     TT_DL(23, sub == 0u);
-                    const uint32_t no = node_offset(child);
-                    const uint4 n0 = buffer_load16(nodes, no), n1 = buffer_load16(nodes, no + 16u),
-                                n2 = buffer_load16(nodes, no + 32u), n3 = buffer_load16(nodes, no + 48u),
-                                n4 = buffer_load16(nodes, no + 64u);
+                    const NodeWords n = load_node<0>(nodes, child);
                     const uint32_t hitmask =
-                        group_or<G>(node_intersect_part<G>(n0, n1, n2, n3, n4, st.ray, st.oct, st.best.t, sub));
-                    st.cg.y = (hitmask & 0xff000000u) | (n0.w >> 24);
-                    st.tg.y = hitmask & 0x00ffffffu;
-                    st.cg.x = n1.x + (uint32_t)st.NodeOffset;
-                    st.tg.x = n1.y + (uint32_t)st.TriOffset;
+                        group_or<G>(node_intersect_part<G>(n.n0, n.n1, n.n2, n.n3, n.n4, st.ray, st.oct, st.best.t, sub));
+                    st.cg = node_group(hitmask, n, st.NodeOffset);
+                    st.tg = tri_group(hitmask, n, st.TriOffset);
                     st.Reps++;
                     if (STATS && sub == 0u) C.nodes++;
                 } else {
@@ -251,32 +264,17 @@ __device__ void wide_phase(const TraceArgs& A, WideState& st, uint2 (*s_stack)[T
             if (!LEAF && st.active && st.tg.y != 0u && st.tlas_ss == -1) {  // :194-219 TLAS leaf -> BLAS
                 const uint32_t mo = firstbithigh(st.tg.y);
                 st.tg.y &= ~(1u << mo);
-                const float4* mp = reinterpret_cast<const float4*>(A.leaf + (st.tg.x + mo));  // LeafMesh
-                const float4 m0 = mp[0], m1 = mp[1], m2 = mp[2];
-                const int4 mo4 = reinterpret_cast<const int4*>(mp)[3];
-                st.mesh_id = reinterpret_cast<const int4*>(mp)[4].x;
-                st.NodeOffset = mo4.y;
-                st.TriOffset = mo4.x;
+                const LeafEntry e = load_leaf_mesh<true>(A.leaf, st.tg.x + mo);
+                st.mesh_id = e.mesh_id;
+                st.NodeOffset = e.off.y;
+                st.TriOffset = e.off.x;
                 bool ok = true;
                 if (st.tg.y != 0u) TT_PUSH(st.tg, ok);
                 if (ok && (st.cg.y & 0xff000000u)) TT_PUSH(st.cg, ok);
                 if (ok) {
                     st.tlas_ss = stack_size;
-                    st.MatOffset = mo4.z;
-                    const LaneRay& ray = st.ray;
-                    LaneRay nr;
-                    nr.dx = fma_(m0.z, ray.dz, fma_(m0.y, ray.dy, m0.x * ray.dx));
-                    nr.dy = fma_(m1.z, ray.dz, fma_(m1.y, ray.dy, m1.x * ray.dx));
-                    nr.dz = fma_(m2.z, ray.dz, fma_(m2.y, ray.dy, m2.x * ray.dx));
-                    nr.ox = fma_(m0.z, ray.oz, fma_(m0.y, ray.oy, m0.x * ray.ox)) + m0.w;
-                    nr.oy = fma_(m1.z, ray.oz, fma_(m1.y, ray.oy, m1.x * ray.ox)) + m1.w;
-                    nr.oz = fma_(m2.z, ray.oz, fma_(m2.y, ray.oy, m2.x * ray.ox)) + m2.w;
-                    nr.ix = rcp_rn(nr.dx);
-                    nr.iy = rcp_rn(nr.dy);
-                    nr.iz = rcp_rn(nr.dz);
-                    st.ray = nr;
-                    st.oct = octant_inv4(st.ray);
-                    st.cg = make_uint2((uint32_t)mo4.w, 0x80000000u);
+                    st.MatOffset = e.off.z;
+                    enter_object_space(e, st.ray, st.oct, st.cg);
                     if (STATS && sub == 0u) C.blas++;
                 } else {
                     st.active = false;
@@ -341,11 +339,7 @@ __device__ void wide_phase(const TraceArgs& A, WideState& st, uint2 (*s_stack)[T
         if (st.active && st.tg.y == 0u && (st.cg.y & 0xff000000u) == 0u) {
             if (stack_size != 0) {
                 if (!LEAF && stack_size == st.tlas_ss) {
-                    st.NodeOffset = (int32_t)A.tlas_base;
-                    st.TriOffset = 0;
-                    st.tlas_ss = -1;
-                    st.ray = st.wray;
-                    st.oct = octant_inv4(st.ray);
+                    leave_blas(A.tlas_base, st.wray, st.NodeOffset, st.TriOffset, st.tlas_ss, st.ray, st.oct);
                 }
                 TT_POP(st.cg);
             } else {
