@@ -225,15 +225,19 @@ tt_status tt_ctx_create(const tt_config* cfg, tt_ctx** out) {
     // Residency check beyond the occupancy API: measured on MI355X, five 32-KiB-LDS blocks were
     // not co-resident (the fifth started only when another exited), consistent with the LDS being
     // allocated per half-CU (2 x 80 KiB). Size every persistent grid so all its blocks are resident.
-    const uint32_t lds_block = tt_trace_lds_bytes();
-    const int lds_cap = lds_block ? 2 * (int)((80u * 1024u) / lds_block) : 8;
+    // (per form: the leaf-TLAS kernels, grid_of[18..23], split their LDS between a shallower stack and a ray pool)
+    auto lds_cap_of = [](bool leaf) {
+        const uint32_t lds_block = tt_trace_lds_bytes(leaf);
+        return lds_block ? 2 * (int)((80u * 1024u) / lds_block) : 8;
+    };
+    const int lds_cap = lds_cap_of(false), lds_cap_leaf = lds_cap_of(true);
     int knob = 0;
     if (const char* e = std::getenv("TT_BLOCKS_PER_CU")) knob = std::atoi(e);  // tuning/diagnostic knob
     // at most 32 waves per CU (8 blocks of 4 waves at the default 256-thread block)
     const int wpb = (int)std::max(1u, tt_trace_block_size() / 64u);
     const int block_cap = std::max(1, 32 / wpb);
     for (int k = 0; k < 24; k++) {
-        int b = std::max(1, std::min(std::min(occ[k], lds_cap), block_cap));
+        int b = std::max(1, std::min(std::min(occ[k], k >= 18 ? lds_cap_leaf : lds_cap), block_cap));
         if (knob > 0 && knob < b) b = knob;
         c->grid_of[k] = (uint32_t)(c->num_cus * b);
     }

@@ -194,7 +194,7 @@ struct TraceArgs {
     const tt_col_data* colors;   // GlobalColors (bounce > 0 with info)
     TraceControl* ctl;
     uint32_t* sticky_overflow;   // stack overflows since the last tt_async_overflows (never reset by launches)
-    uint2* spill;                // traversal-stack entries beyond TT_LDS_STACK, [entry][thread]
+    uint2* spill;                // traversal-stack entries beyond the LDS part, [entry][thread]
     unsigned long long* diag_times;  // TT_DIAG_TIMES builds: per wave (start, end, rays)
     uint32_t n_rays;             // rays to trace; with n_rays_dev: the capacity
     const uint32_t* n_rays_dev;  // nullable: device-resident count (BufferSizes[CurBounce].tracerays),

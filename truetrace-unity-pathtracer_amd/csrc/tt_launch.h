@@ -10,7 +10,7 @@ hipError_t tt_launch_shadow_accumulate(const ShadowArgs* a, const float4* vis, h
 void tt_shadow_occupancy_table(int* out4);
 uint32_t tt_trace_block_size();
 uint32_t tt_trace_spill_entries();
-uint32_t tt_trace_lds_bytes();
+uint32_t tt_trace_lds_bytes(bool leaf);
 hipError_t tt_launch_generate(const float* c2w, const float* ip, uint32_t w, uint32_t h, float near_plane, float far_plane,
                               int32_t jitter, int32_t frames, int32_t max_bounce, tt_ray_data* rays, hipStream_t st);
 hipError_t tt_launch_bounce(tt_ray_data* rays, uint32_t src_off, uint32_t dst_off, uint32_t n, float far_plane,

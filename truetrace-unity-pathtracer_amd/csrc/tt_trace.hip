@@ -17,9 +17,11 @@
 #include "tt_launch.h"
 #include "tt_wide.h"
 
-// TT_REFILL_MIN of the leaf-TLAS kernels (trace_body<LEAF>), whose ray start is cheaper: a knob of its own
+// TT_REFILL_MIN of the leaf-TLAS kernels (trace_body<LEAF>), whose ray start is cheaper: a knob of its own.
+// With the prepared-ray pool (TT_LEAF_POOL) the headline is flat over 14 - 20 and falls below 12 (4: -5 %): a
+// refill that only reads a record still costs the wave an iteration with its record writes (profiles/r12/refill/).
 #ifndef TT_LEAF_REFILL_MIN
-#define TT_LEAF_REFILL_MIN TT_REFILL_MIN
+#define TT_LEAF_REFILL_MIN (TT_LEAF_POOL ? 16 : TT_REFILL_MIN)
 #endif
 
 namespace {
@@ -177,11 +179,21 @@ __device__ __forceinline__ bool root_leaf_hit(const RootLeaf& R, const LaneRay& 
 // and no lane keeps tlas_ss, best.mesh_id or (LEAF == 1; LEAF == 2 keeps it for the INFO = 2 record) the world
 // ray: fewer VGPRs (more resident waves), a cheaper ray start, no TLAS-leaf test after a node step and no
 // BLAS-exit test in the advance. The arithmetic of a ray and its order are the generic kernel's, so results are
-// bit-identical. Never with STATS, MATCHECK or ORD.
+// bit-identical. Never with STATS, MATCHECK or ORD. With TT_LEAF_POOL the ray start runs once per dequeued chunk,
+// for all 64 rays at full wave width, into a per-wave pool in LDS that the refills read (POOL below).
 template <bool STATS, bool MATCHECK, int INFO, bool IND, bool ORD, int LEAF = 0>
 __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     static_assert(!LEAF || (!STATS && !MATCHECK && !ORD), "the leaf-TLAS form has no stats / material / order variants");
-    __shared__ uint2 s_stack[TT_LDS_STACK][TT_BLOCK];
+    // POOL (the leaf-TLAS form, TT_LEAF_POOL): the rays of a dequeued chunk are set up by all 64 lanes at once into
+    // s_pool, one 48-B record per ray as three 16-B words [word][slot]: (o.xyz, d.x) (d.yz, i.xy) (i.z, PixelIndex,
+    // Data.w, octant | root hit << 31), o / d / i the ray in the instance's object space. A refilled lane reads the
+    // record of its slot (slot = work index & 63: a reservation is one chunk-aligned chunk of TT_CHUNK_BIG rays).
+    constexpr bool POOL = LEAF != 0 && TT_LEAF_POOL != 0;
+    constexpr int tt_lds_depth = lds_depth_of<LEAF>();  // the LDS part of the stack (TT_PUSH / TT_POP)
+    static_assert(!POOL || TT_CHUNK_BIG == TT_WAVE, "the prepared-ray pool holds one chunk, one slot per lane");
+    __shared__ uint2 s_stack[tt_lds_depth][TT_BLOCK];
+    __shared__ uint4 s_pool[POOL ? 3 : 1][TT_BLOCK];
+    (void)s_pool;
     // (read before the kernel's first store, so the compiler can prove the loads unclobbered and make them scalar)
     LeafEntry L{};  // LEAF: the LeafMesh record of the one instance
     if (LEAF) L = load_leaf_mesh<true>(A.leaf, A.root.base_tri + firstbithigh(A.root.bits));
@@ -239,6 +251,18 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     uint32_t d_lead_same = 0, d_uniform = 0;  // node-step uniformity (lanes sharing the first lane's node)
     // the world-space ray (ray2, IntersectionKernels.compute:151), kept in registers
     auto world_ray = [&]() -> LaneRay { return wray; };
+    // POOL: work index -> ray index (8x8 screen tiles for full-frame primary batches), as the per-lane setup has it
+    auto ray_of = [&](uint32_t widx) -> uint32_t {
+        uint32_t local = widx;
+        if (swizzle) {
+            const uint32_t tw = A.width >> 3;
+            const uint32_t t = widx >> 6, l = widx & 63u;
+            const uint32_t ty = fastdiv(t, A.div_tiles), tx = t - ty * tw;
+            local = (ty * 8u + (l >> 3)) * A.width + tx * 8u + (l & 7u);
+        }
+        return A.ray_offset + local;
+    };
+    (void)ray_of;
 
 #if TT_ROOT_LEAF
     const bool rl_ok = A.root.ok != 0u;  // a kernel argument: wave-uniform
@@ -347,7 +371,100 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
             pool_next = pt.pool_next;
             pool_end = pt.pool_end;
             more = pt.more;
-            if ((int32_t)tg.y < 0 && widx != 0xffffffffu) {
+            if constexpr (POOL) {
+                const uint32_t pcol = tid - lane;  // the wave's pool columns
+                const bool take = (int32_t)tg.y < 0 && widx != 0xffffffffu;
+                // slots left from the previous chunk are read before the new chunk overwrites the pool
+                const bool take_left = take && lane_prefix(idle) < min(avail, n_idle);
+                uint4 p0 = make_uint4(0u, 0u, 0u, 0u), p1 = p0, p2 = p0;
+                if (take_left) {
+                    const uint32_t slot = pcol + (widx & 63u);
+                    p0 = s_pool[0][slot];
+                    p1 = s_pool[1][slot];
+                    p2 = s_pool[2][slot];
+                }
+                // (one wave owns the pool and its LDS accesses execute in order: these only keep the compiler from
+                // moving the reads and writes of different lanes' slots across each other)
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                if (new_count > 0) {  // wave-uniform: every lane, busy or idle, sets up ray new_base + lane
+                    TT_DB(4);
+                    uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0;
+                    if (lane < new_count) {  // (all 64 but in a launch's last chunk)
+                        const uint4* rp = reinterpret_cast<const uint4*>(A.rays + ray_of(new_base + lane));
+                        const uint4 r0 = rp[0], r1 = rp[1];
+                        float cw = 0.0f;
+                        if (INFO == 2) cw = (r0.w < A.n_pixels) ? A.colors[r0.w].Data[3] : 0.0f;
+                        LaneRay r;
+                        r.ox = __uint_as_float(r0.x);
+                        r.oy = __uint_as_float(r0.y);
+                        r.oz = __uint_as_float(r0.z);
+                        r.dx = __uint_as_float(r1.x);
+                        r.dy = __uint_as_float(r1.y);
+                        r.dz = __uint_as_float(r1.z);
+                        r.ix = rcp_rn(r.dx);
+                        r.iy = rcp_rn(r.dy);
+                        r.iz = rcp_rn(r.dz);
+                        // the root's node step; a hit is the TLAS leaf -> BLAS switch (nothing to push)
+                        uint32_t o = 0u;
+                        uint2 g = make_uint2(0u, 0u);
+                        if (root_leaf_hit(A.root, r, A.far_plane)) enter_object_space(L, r, o, g);
+                        q0 = make_uint4(__float_as_uint(r.ox), __float_as_uint(r.oy), __float_as_uint(r.oz),
+                                        __float_as_uint(r.dx));
+                        q1 = make_uint4(__float_as_uint(r.dy), __float_as_uint(r.dz), __float_as_uint(r.ix),
+                                        __float_as_uint(r.iy));
+                        q2 = make_uint4(__float_as_uint(r.iz), r0.w, __float_as_uint(cw), o | g.y);
+                    }
+                    s_pool[0][tid] = q0;
+                    s_pool[1][tid] = q1;
+                    s_pool[2][tid] = q2;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                if (take && !take_left) {
+                    const uint32_t slot = pcol + (widx & 63u);
+                    p0 = s_pool[0][slot];
+                    p1 = s_pool[1][slot];
+                    p2 = s_pool[2][slot];
+                }
+                if (take) {
+                    TT_DL(19, true);
+                    ray_index = ray_of(widx);
+                    ray.ox = __uint_as_float(p0.x);
+                    ray.oy = __uint_as_float(p0.y);
+                    ray.oz = __uint_as_float(p0.z);
+                    ray.dx = __uint_as_float(p0.w);
+                    ray.dy = __uint_as_float(p1.x);
+                    ray.dz = __uint_as_float(p1.y);
+                    ray.ix = __uint_as_float(p1.z);
+                    ray.iy = __uint_as_float(p1.w);
+                    ray.iz = __uint_as_float(p2.x);
+                    pix = p2.y;
+                    col_w = __uint_as_float(p2.z);
+                    oct = p2.w & 0x7fffffffu;
+                    // a ray that missed the root's box starts with the empty group: the advance finishes it
+                    cg = make_uint2((p2.w & 0x80000000u) ? (uint32_t)L.off.w : 0u, p2.w & 0x80000000u);
+                    if (LEAF == 2) {  // the world ray of the INFO = 2 record: the chunk's setup has just read the lines
+                        const uint4* rp = reinterpret_cast<const uint4*>(A.rays + ray_index);
+                        const uint4 r0 = rp[0], r1 = rp[1];
+                        wray.ox = __uint_as_float(r0.x);
+                        wray.oy = __uint_as_float(r0.y);
+                        wray.oz = __uint_as_float(r0.z);
+                        wray.dx = __uint_as_float(r1.x);
+                        wray.dy = __uint_as_float(r1.y);
+                        wray.dz = __uint_as_float(r1.z);
+                    }
+                    best.t = A.far_plane;
+                    best.u = 0.0f;
+                    best.v = 0.0f;
+                    best.mesh_id = 0;
+                    best.tri_id = -1;
+                    tg = make_uint2(0u, 0u);
+                    stack_size = 0;
+                    Reps = 1;
+                }
+            }
+            if (!POOL && (int32_t)tg.y < 0 && widx != 0xffffffffu) {
                 TT_DB(4);
                 TT_DL(19, true);
                 // work index -> ray index (8x8 screen tiles for full-frame primary batches)
@@ -654,7 +771,13 @@ hipError_t tt_trace_occupancy_table(int* out24) {
 
 uint32_t tt_trace_block_size() { return TT_BLOCK; }
 uint32_t tt_trace_chunk_rays() { return TT_CHUNK_BIG; }
-uint32_t tt_trace_lds_bytes() { return (uint32_t)(TT_LDS_STACK * TT_BLOCK * sizeof(uint2)); }
+// LDS of one block: the stack entries its form keeps there, plus the leaf-TLAS form's prepared-ray pool
+uint32_t tt_trace_lds_bytes(bool leaf) {
+    const uint32_t stack = (uint32_t)((leaf ? lds_depth_of<1>() : lds_depth_of<0>()) * TT_BLOCK * sizeof(uint2));
+    return stack + (leaf && TT_LEAF_POOL ? (uint32_t)(3 * TT_BLOCK * sizeof(uint4)) : 0u);
+}
+// (one spill area serves every form: sized for the shallowest LDS part)
 uint32_t tt_trace_spill_entries() {
-    return TT_LDS_STACK >= TT_STACK_SIZE ? 0u : (uint32_t)(TT_STACK_SIZE - TT_LDS_STACK);
+    constexpr int depth = lds_depth_of<1>() < lds_depth_of<0>() ? lds_depth_of<1>() : lds_depth_of<0>();
+    return depth >= TT_STACK_SIZE ? 0u : (uint32_t)(TT_STACK_SIZE - depth);
 }

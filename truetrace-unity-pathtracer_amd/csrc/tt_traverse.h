@@ -46,6 +46,16 @@
 #ifndef TT_LDS_STACK
 #define TT_LDS_STACK 12   // stack entries kept in LDS; deeper entries spill to a global area
 #endif
+// The leaf-TLAS closest-hit kernels (tt_trace.hip, trace_body<LEAF>) set the rays of a dequeued chunk up at full
+// width into a per-wave pool of prepared rays in LDS (TT_LEAF_POOL 1; 0: the per-lane setup at refill, for A/B).
+// The pool takes 3 KiB of the wave's LDS, so those kernels keep TT_LEAF_LDS_STACK stack entries there: pool + stack
+// = the 6 KiB of the other kernels, and as many one-wave blocks stay resident per CU.
+#ifndef TT_LEAF_POOL
+#define TT_LEAF_POOL 1
+#endif
+#ifndef TT_LEAF_LDS_STACK
+#define TT_LEAF_LDS_STACK 6
+#endif
 #ifndef TT_WAVES_PER_EU
 #define TT_WAVES_PER_EU 0 // __launch_bounds__ min waves per SIMD (0: compiler default)
 #endif
@@ -619,14 +629,22 @@ int occupancy_of(Kernel kernel) {
 
 }  // namespace
 
-// Traversal stack: entries [0, TT_LDS_STACK) in LDS s_stack[entry][thread] (64 distinct banks per
+// Traversal stack: entries [0, tt_lds_depth) in LDS s_stack[entry][thread] (64 distinct banks per
 // wave access), deeper entries in a global spill area [entry][grid thread]. Expect in scope:
-// s_stack, spill, spill_stride, gtid, tid, stack_size.
+// s_stack, spill, spill_stride, gtid, tid, stack_size. tt_lds_depth is TT_LDS_STACK unless the loop
+// declares its own (the leaf-TLAS closest-hit loop and its drain: lds_depth_of<LEAF>()).
+namespace {
+constexpr int tt_lds_depth = TT_LDS_STACK;
+template <int LEAF>
+constexpr int lds_depth_of() {
+    return LEAF != 0 && TT_LEAF_POOL != 0 ? TT_LEAF_LDS_STACK : TT_LDS_STACK;
+}
+}  // namespace
 #if TT_PUSH_FAST  // one compare on the common path (an LDS entry is free); overflow / spill only beyond it
 #define TT_PUSH(val, ok)                                                            \
     do {                                                                            \
-        if (TT_LDS_STACK >= TT_STACK_SIZE || stack_size < TT_LDS_STACK) {           \
-            if (TT_LDS_STACK >= TT_STACK_SIZE && stack_size == TT_STACK_SIZE) {     \
+        if (tt_lds_depth >= TT_STACK_SIZE || stack_size < tt_lds_depth) {           \
+            if (tt_lds_depth >= TT_STACK_SIZE && stack_size == TT_STACK_SIZE) {     \
                 ok = false;                                                         \
             } else {                                                                \
                 s_stack[stack_size][tid] = (val);                                   \
@@ -635,7 +653,7 @@ int occupancy_of(Kernel kernel) {
         } else if (stack_size == TT_STACK_SIZE) {                                   \
             ok = false;                                                             \
         } else {                                                                    \
-            spill[(size_t)(stack_size - TT_LDS_STACK) * spill_stride + gtid] = (val); \
+            spill[(size_t)(stack_size - tt_lds_depth) * spill_stride + gtid] = (val); \
             stack_size++;                                                           \
         }                                                                           \
     } while (0)
@@ -645,10 +663,10 @@ int occupancy_of(Kernel kernel) {
         if (stack_size == TT_STACK_SIZE) {                                          \
             ok = false;                                                             \
         } else {                                                                    \
-            if (TT_LDS_STACK >= TT_STACK_SIZE || stack_size < TT_LDS_STACK)         \
+            if (tt_lds_depth >= TT_STACK_SIZE || stack_size < tt_lds_depth)         \
                 s_stack[stack_size][tid] = (val);                                   \
             else                                                                    \
-                spill[(size_t)(stack_size - TT_LDS_STACK) * spill_stride + gtid] = (val); \
+                spill[(size_t)(stack_size - tt_lds_depth) * spill_stride + gtid] = (val); \
             stack_size++;                                                           \
         }                                                                           \
     } while (0)
@@ -656,10 +674,10 @@ int occupancy_of(Kernel kernel) {
 #define TT_POP(dst)                                                                 \
     do {                                                                            \
         --stack_size;                                                               \
-        if (TT_LDS_STACK >= TT_STACK_SIZE || stack_size < TT_LDS_STACK)             \
+        if (tt_lds_depth >= TT_STACK_SIZE || stack_size < tt_lds_depth)             \
             dst = s_stack[stack_size][tid];                                         \
         else                                                                        \
-            dst = spill[(size_t)(stack_size - TT_LDS_STACK) * spill_stride + gtid]; \
+            dst = spill[(size_t)(stack_size - tt_lds_depth) * spill_stride + gtid]; \
     } while (0)
 
 #endif  // TT_TRAVERSE_H

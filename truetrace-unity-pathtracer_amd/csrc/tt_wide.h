@@ -216,6 +216,7 @@ __device__ void wide_phase(const TraceArgs& A, WideState& st, uint2 (*s_stack)[T
     const uint32_t base = lane & ~(uint32_t)(G - 1);
     const uint32_t tid = st.scol, gtid = st.gcol;  // the stack the TT_PUSH / TT_POP macros address
     int32_t& stack_size = st.stack_size;
+    constexpr int tt_lds_depth = lds_depth_of<LEAF>();  // the LDS part of the stack of the loop that drains
     while (true) {
         const uint64_t lead = __ballot(st.active && sub == 0u);
         const uint32_t n = (uint32_t)__popcll(lead);
