@@ -11,6 +11,8 @@ C4 (argument c4). Counters (csrc/tt_trace.hip, tt_wide.h; wave executions unless
  17 lanes in node steps   18 lanes in triangle passes   19 lanes refilled
  20/21/22 drain node steps (G = 2/4/8)   23 rays in drain node steps
  24/25/26 drain triangle passes (G = 2/4/8)   27 rays in drain triangle passes
+ 28 chunk-setup node steps (TT_LEAF_ROOT_STEP: the BLAS root's step of a whole chunk)
+ 29 lanes in chunk-setup node steps (rays that hit the TLAS root's box)
 
 Weighted by each block's static VALU count (tools/isa_blocks.py on the product kernel's ISA; the
 table is --static JSON), this gives VALU per ray by block. Output: JSON on stdout."""
@@ -25,7 +27,7 @@ NAMES = ["iterations", "record_batches", "refills", "dequeues", "ray_setups", "n
          "tlas_leaf", "tri_passes", "advance", "pops", "blas_exits", "drain_entries", "drain_iters_g2",
          "drain_iters_g4", "drain_iters_g8", "lanes_node", "lanes_tri", "lanes_refilled", "drain_node_g2",
          "drain_node_g4", "drain_node_g8", "drain_node_rays", "drain_tri_g2", "drain_tri_g4", "drain_tri_g8",
-         "drain_tri_rays"]
+         "drain_tri_rays", "setup_node_steps", "lanes_setup_node"]
 
 
 def main():
@@ -70,6 +72,9 @@ def main():
         rec["lanes_per_node_step"] = round(c[17] / max(c[6], 1), 2)
         rec["lanes_per_tri_pass"] = round(c[18] / max(c[9], 1), 2)
         rec["lanes_per_refill"] = round(c[19] / max(c[4], 1), 2)
+        rec["lanes_per_setup_node_step"] = round(c[29] / max(c[28], 1), 2)
+        # every node step of a ray: the loop's lanes, the drain's rays and the chunk setup's lanes
+        rec["node_steps_per_ray"] = round((c[17] + c[23] + (c[29] if c[28] else 0)) / n, 4)
         rec["drain_node_share"] = round(c[23] / max(c[17] + c[23], 1), 4)
         out["launches"][f"bounce{b}"] = rec
         print(f"[diag] bounce {b}: {rec}", file=sys.stderr, flush=True)

@@ -188,7 +188,15 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     // s_pool, one 48-B record per ray as three 16-B words [word][slot]: (o.xyz, d.x) (d.yz, i.xy) (i.z, PixelIndex,
     // Data.w, octant | root hit << 31), o / d / i the ray in the instance's object space. A refilled lane reads the
     // record of its slot (slot = work index & 63: a reservation is one chunk-aligned chunk of TT_CHUNK_BIG rays).
+    // ROOTSTEP (TT_LEAF_ROOT_STEP): the setup also makes the ray's first node step of the loop -- the BLAS root, L.off.w,
+    // with t_max = FarPlane, the same node for every ray of the launch -- at full width, from wave-uniform loads of
+    // the node. The step's child base, triangle base and imask are wave-uniform, so the record stays 48 B: word 10 is
+    // octant | root box hit << 31 and word 11 the step's 32-bit hit mask (0 for a ray that missed the root's box).
+    // Data.w (INFO 2), whose place that takes, is only ever tested by write_record: the setup makes the test and a
+    // ray that fails it carries PixelIndex 0xffffffff, which writes no texel either. A refilled lane starts after
+    // the step: Reps 2, the hit inner children in cg and the hit leaf triangles in tg, or an empty group.
     constexpr bool POOL = LEAF != 0 && TT_LEAF_POOL != 0;
+    constexpr bool ROOTSTEP = POOL && TT_LEAF_ROOT_STEP != 0;
     constexpr int tt_lds_depth = lds_depth_of<LEAF>();  // the LDS part of the stack (TT_PUSH / TT_POP)
     static_assert(!POOL || TT_CHUNK_BIG == TT_WAVE, "the prepared-ray pool holds one chunk, one slot per lane");
     __shared__ uint2 s_stack[tt_lds_depth][TT_BLOCK];
@@ -197,6 +205,15 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     // (read before the kernel's first store, so the compiler can prove the loads unclobbered and make them scalar)
     LeafEntry L{};  // LEAF: the LeafMesh record of the one instance
     if (LEAF) L = load_leaf_mesh<true>(A.leaf, A.root.base_tri + firstbithigh(A.root.bits));
+    // ROOTSTEP: the wave-uniform words of the BLAS root's step that a refill needs (node_group / tri_group): the child
+    // and triangle bases and the imask. The whole node is read again by each chunk setup and lives only there.
+    uint32_t root_cg_x = 0, root_tg_x = 0, root_imask = 0;
+    if (ROOTSTEP) {
+        const NodeWords n = load_node_uniform(A.nodes, A.n_nodes, (uint32_t)L.off.w);
+        root_cg_x = n.n1.x + (uint32_t)L.off.y;
+        root_tg_x = n.n1.y + (uint32_t)L.off.x;
+        root_imask = n.n0.w >> 24;
+    }
     const uint32_t tid = threadIdx.x;
     zero_next_control(A.ctl_next, tid);
     const uint32_t gtid = blockIdx.x * TT_BLOCK + tid;
@@ -376,12 +393,63 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                 const bool take = (int32_t)tg.y < 0 && widx != 0xffffffffu;
                 // slots left from the previous chunk are read before the new chunk overwrites the pool
                 const bool take_left = take && lane_prefix(idle) < min(avail, n_idle);
+                // a lane's start from the record of its slot
+                auto start_ray = [&](const uint4 p0, const uint4 p1, const uint4 p2) {
+                    TT_DL(19, true);
+                    ray_index = ray_of(widx);
+                    ray.ox = __uint_as_float(p0.x);
+                    ray.oy = __uint_as_float(p0.y);
+                    ray.oz = __uint_as_float(p0.z);
+                    ray.dx = __uint_as_float(p0.w);
+                    ray.dy = __uint_as_float(p1.x);
+                    ray.dz = __uint_as_float(p1.y);
+                    ray.ix = __uint_as_float(p1.z);
+                    ray.iy = __uint_as_float(p1.w);
+                    ray.iz = __uint_as_float(p2.x);
+                    pix = p2.y;
+                    if (ROOTSTEP) {
+                        col_w = -1.0f;  // (the setup has made write_record's test of Data.w: see there)
+                        oct = p2.z & 0x7fffffffu;
+                        // node_group / tri_group of the setup's step. Without a hit inner child the node group is
+                        // empty -- in the loop the advance follows such a step at once, here the node phase comes
+                        // first -- and so is a ray's that missed the root's box (mask 0): the advance finishes it
+                        const uint32_t inner = p2.w & 0xff000000u;
+                        cg = make_uint2(root_cg_x, inner ? (inner | root_imask) : 0u);
+                        tg = make_uint2(root_tg_x, p2.w & 0x00ffffffu);
+                        Reps = (p2.z & 0x80000000u) ? 2 : 1;
+                    } else {
+                        col_w = __uint_as_float(p2.z);
+                        oct = p2.w & 0x7fffffffu;
+                        // a ray that missed the root's box starts with the empty group: the advance finishes it
+                        cg = make_uint2((p2.w & 0x80000000u) ? (uint32_t)L.off.w : 0u, p2.w & 0x80000000u);
+                    }
+                    if (LEAF == 2) {  // the world ray of the INFO = 2 record: the chunk's setup has just read the lines
+                        const uint4* rp = reinterpret_cast<const uint4*>(A.rays + ray_index);
+                        const uint4 r0 = rp[0], r1 = rp[1];
+                        wray.ox = __uint_as_float(r0.x);
+                        wray.oy = __uint_as_float(r0.y);
+                        wray.oz = __uint_as_float(r0.z);
+                        wray.dx = __uint_as_float(r1.x);
+                        wray.dy = __uint_as_float(r1.y);
+                        wray.dz = __uint_as_float(r1.z);
+                    }
+                    best.t = A.far_plane;
+                    best.u = 0.0f;
+                    best.v = 0.0f;
+                    best.mesh_id = 0;
+                    best.tri_id = -1;
+                    if (!ROOTSTEP) tg = make_uint2(0u, 0u);
+                    stack_size = 0;
+                    if (!ROOTSTEP) Reps = 1;
+                };
                 uint4 p0 = make_uint4(0u, 0u, 0u, 0u), p1 = p0, p2 = p0;
                 if (take_left) {
                     const uint32_t slot = pcol + (widx & 63u);
                     p0 = s_pool[0][slot];
                     p1 = s_pool[1][slot];
                     p2 = s_pool[2][slot];
+                    // ROOTSTEP: started here, so that the record is not held in registers across the setup
+                    if (ROOTSTEP) start_ray(p0, p1, p2);
                 }
                 // (one wave owns the pool and its LDS accesses execute in order: these only keep the compiler from
                 // moving the reads and writes of different lanes' slots across each other)
@@ -390,6 +458,8 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                 if (new_count > 0) {  // wave-uniform: every lane, busy or idle, sets up ray new_base + lane
                     TT_DB(4);
                     uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0;
+                    NodeWords rn{};  // ROOTSTEP: the BLAS root, from device memory at every setup, in SGPRs
+                    if (ROOTSTEP) rn = load_node_uniform(A.nodes, A.n_nodes, (uint32_t)L.off.w);
                     if (lane < new_count) {  // (all 64 but in a launch's last chunk)
                         const uint4* rp = reinterpret_cast<const uint4*>(A.rays + ray_of(new_base + lane));
                         const uint4 r0 = rp[0], r1 = rp[1];
@@ -408,16 +478,37 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                         // the root's node step; a hit is the TLAS leaf -> BLAS switch (nothing to push)
                         uint32_t o = 0u;
                         uint2 g = make_uint2(0u, 0u);
-                        if (root_leaf_hit(A.root, r, A.far_plane)) enter_object_space(L, r, o, g);
+                        const bool root_hit = root_leaf_hit(A.root, r, A.far_plane);
+                        TT_DL(29, root_hit);
+                        if (root_hit) enter_object_space(L, r, o, g);
                         q0 = make_uint4(__float_as_uint(r.ox), __float_as_uint(r.oy), __float_as_uint(r.oz),
                                         __float_as_uint(r.dx));
                         q1 = make_uint4(__float_as_uint(r.dy), __float_as_uint(r.dz), __float_as_uint(r.ix),
                                         __float_as_uint(r.iy));
                         q2 = make_uint4(__float_as_uint(r.iz), r0.w, __float_as_uint(cw), o | g.y);
+                        if (ROOTSTEP) {
+                            // write_record's test of Data.w (INFO 2) is made here: where it fails the record carries
+                            // no pixel (a PixelIndex past the frame writes no texel either)
+                            if (INFO == 2 && !(cw == -1.0f || (float)A.bounce == cw)) q2.y = 0xffffffffu;
+                            q2.z = o | g.y;
+                            q2.w = 0u;
+                            // (the record goes out before the step, which then holds only what it reads; the step
+                            // adds its mask)
+                            s_pool[0][tid] = q0;
+                            s_pool[1][tid] = q1;
+                            s_pool[2][tid] = q2;
+                            // the BLAS root's node step, as the loop would make it first (best.t is FarPlane there)
+                            if (root_hit) {
+                                TT_DB(28);
+                                s_pool[2][tid].w = node_intersect(rn.n0, rn.n1, rn.n2, rn.n3, rn.n4, r, o, A.far_plane);
+                            }
+                        }
                     }
-                    s_pool[0][tid] = q0;
-                    s_pool[1][tid] = q1;
-                    s_pool[2][tid] = q2;
+                    if (!ROOTSTEP) {  // (ROOTSTEP: the slots past a launch's last ray keep their old words, never read)
+                        s_pool[0][tid] = q0;
+                        s_pool[1][tid] = q1;
+                        s_pool[2][tid] = q2;
+                    }
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
@@ -426,43 +517,9 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                     p0 = s_pool[0][slot];
                     p1 = s_pool[1][slot];
                     p2 = s_pool[2][slot];
+                    if (ROOTSTEP) start_ray(p0, p1, p2);
                 }
-                if (take) {
-                    TT_DL(19, true);
-                    ray_index = ray_of(widx);
-                    ray.ox = __uint_as_float(p0.x);
-                    ray.oy = __uint_as_float(p0.y);
-                    ray.oz = __uint_as_float(p0.z);
-                    ray.dx = __uint_as_float(p0.w);
-                    ray.dy = __uint_as_float(p1.x);
-                    ray.dz = __uint_as_float(p1.y);
-                    ray.ix = __uint_as_float(p1.z);
-                    ray.iy = __uint_as_float(p1.w);
-                    ray.iz = __uint_as_float(p2.x);
-                    pix = p2.y;
-                    col_w = __uint_as_float(p2.z);
-                    oct = p2.w & 0x7fffffffu;
-                    // a ray that missed the root's box starts with the empty group: the advance finishes it
-                    cg = make_uint2((p2.w & 0x80000000u) ? (uint32_t)L.off.w : 0u, p2.w & 0x80000000u);
-                    if (LEAF == 2) {  // the world ray of the INFO = 2 record: the chunk's setup has just read the lines
-                        const uint4* rp = reinterpret_cast<const uint4*>(A.rays + ray_index);
-                        const uint4 r0 = rp[0], r1 = rp[1];
-                        wray.ox = __uint_as_float(r0.x);
-                        wray.oy = __uint_as_float(r0.y);
-                        wray.oz = __uint_as_float(r0.z);
-                        wray.dx = __uint_as_float(r1.x);
-                        wray.dy = __uint_as_float(r1.y);
-                        wray.dz = __uint_as_float(r1.z);
-                    }
-                    best.t = A.far_plane;
-                    best.u = 0.0f;
-                    best.v = 0.0f;
-                    best.mesh_id = 0;
-                    best.tri_id = -1;
-                    tg = make_uint2(0u, 0u);
-                    stack_size = 0;
-                    Reps = 1;
-                }
+                if (!ROOTSTEP && take) start_ray(p0, p1, p2);
             }
             if (!POOL && (int32_t)tg.y < 0 && widx != 0xffffffffu) {
                 TT_DB(4);

@@ -56,6 +56,12 @@
 #ifndef TT_LEAF_LDS_STACK
 #define TT_LEAF_LDS_STACK 6
 #endif
+// With the pool, the chunk setup also makes every ray's first node step of the loop, the one at the instance's BLAS
+// root with t_max = FarPlane, for all 64 rays at once from wave-uniform loads of the node; the pool record carries
+// the step's hit mask and a refilled lane starts after it (TT_LEAF_ROOT_STEP 1; 0: the step stays in the loop, A/B).
+#ifndef TT_LEAF_ROOT_STEP
+#define TT_LEAF_ROOT_STEP 1
+#endif
 #ifndef TT_WAVES_PER_EU
 #define TT_WAVES_PER_EU 0 // __launch_bounds__ min waves per SIMD (0: compiler default)
 #endif
@@ -259,6 +265,27 @@ __device__ __forceinline__ NodeWords load_node(__amdgpu_buffer_rsrc_t nodes, uin
     return NodeWords{buffer_load16<CPOL>(nodes, no), buffer_load16<CPOL>(nodes, no + 16u),
                      buffer_load16<CPOL>(nodes, no + 32u), buffer_load16<CPOL>(nodes, no + 48u),
                      buffer_load16<CPOL>(nodes, no + 64u)};
+}
+// The 80 B of node `node`, the same for the whole wave, into SGPRs: five scalar 16-B loads with one wait (in one asm
+// statement: the compiler makes a load scalar only where it can prove the memory unwritten by the kernel so far,
+// and it does not count an asm load, so the wait is inside). Read-only data of the launch, so the scalar cache is
+// as good as the vector one. Bounded like the buffer loads: a node outside the array reads zeros.
+__device__ __forceinline__ NodeWords load_node_uniform(const uint4* nodes, uint32_t n_nodes, uint32_t node) {
+    u32x4 a = {0u, 0u, 0u, 0u}, b = a, c = a, d = a, e = a;
+    if (node < n_nodes) {
+        const char* p = reinterpret_cast<const char*>(nodes) + (size_t)node * TT_NODE_STRIDE;
+        asm volatile("s_nop 4\n\t"
+                     "s_load_dwordx4 %0, %5, 0x0\n\t"
+                     "s_load_dwordx4 %1, %5, 0x10\n\t"
+                     "s_load_dwordx4 %2, %5, 0x20\n\t"
+                     "s_load_dwordx4 %3, %5, 0x30\n\t"
+                     "s_load_dwordx4 %4, %5, 0x40\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&s"(a), "=&s"(b), "=&s"(c), "=&s"(d), "=&s"(e)
+                     : "s"(p));
+    }
+    return NodeWords{make_uint4(a.x, a.y, a.z, a.w), make_uint4(b.x, b.y, b.z, b.w), make_uint4(c.x, c.y, c.z, c.w),
+                     make_uint4(d.x, d.y, d.z, d.w), make_uint4(e.x, e.y, e.z, e.w)};
 }
 // :170-187 a node's hit mask folded into the two groups at the ray's level: the node group (child base; hit
 // inner children | imask) and the triangle group (triangle base; hit leaf bits). Returned by value: one function
