@@ -202,6 +202,13 @@ namespace TrueTrace.Hip
         [DllImport(Lib)] public static extern unsafe TTStatus tt_scene_assemble_objects(IntPtr ctx, IntPtr* objects,
             uint nObjects, void* tlasNodes, uint tlasRegion, int* tlasIndices, uint nTlas, void* meshData, uint nMesh,
             void* materials, uint nMat);
+        // A mesh built into an object on the device (BuildTotal as two kernels around the GPU builder); presorted is a
+        // HOST array of 3 x n indices or null (device presort; TTStatus.Unsupported: retry with Array.Sort's lists)
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_object_build_device(IntPtr ctx, ref TTMeshInput mesh,
+            int* presorted, uint flags, out IntPtr obj, out TTObjectBuildInfo info);
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_object_read(IntPtr ctx, IntPtr obj, void* nodes, void* tris,
+            int* leafOfTriangle);
+        [DllImport(Lib)] public static extern TTStatus tt_object_leaf_order_device(IntPtr obj, out IntPtr leafOfTriangleDev);
         // kernel_heightmap / kernel_shadow_heightmap (IntersectionKernels.compute:508-710); pointers are host or HIP
         // device memory as the flags say (TT_TRACE_DEVICE_PTRS); the _indirect forms read their count on the device.
         [DllImport(Lib)] public static extern TTStatus tt_trace_heightmap(IntPtr ctx, ref TTTraceParams p, IntPtr globalRays,
@@ -687,6 +694,18 @@ namespace TrueTrace.Hip
             return new TrueTraceHipObject(obj);
         }
 
+        /// tt_object_build_device: a ParentObject's mesh built into an object on this tracer's device, with no
+        /// CudaTriangle in managed memory. presorted: BVH2Builder's three Array.Sort lists (3 x n), or null for the
+        /// device presort; on TTStatus.Unsupported the caller sorts and calls again.
+        public unsafe TrueTraceHipObject BuildObject(ref TTMeshInput mesh, int[] presorted, bool devicePointers,
+                                                     out TTObjectBuildInfo info)
+        {
+            IntPtr obj;
+            fixed (int* p = presorted)
+                Check(Native.tt_object_build_device(m_ctx, ref mesh, p, devicePointers ? 1u : 0u, out obj, out info));
+            return new TrueTraceHipObject(obj);
+        }
+
         /// SetMeshTraceBuffers for a changed object set, on the device (tt_scene_assemble_objects): `objects` in
         /// layout order (RenderQue parents, then InstanceData parents); the host supplies only the TLAS-region
         /// nodes [0, 2 * (parents + instances)), TLASBVH8Indices, _MeshData and the materials.
@@ -727,6 +746,28 @@ namespace TrueTrace.Hip
         public ulong bytes;
     }
 
+    /// tt_mesh_input: one ParentObject's merged object-space mesh; host pointers, or GraphicsBuffer native pointers
+    /// with TTTraceFlags.DevicePtrs. normals, tangents, uvs and matdat may be IntPtr.Zero.
+    [StructLayout(LayoutKind.Sequential)]
+    public struct TTMeshInput
+    {
+        public IntPtr positions;
+        public uint nVertices;
+        public IntPtr normals, tangents, uvs, indices;
+        public uint nIndices;
+        public IntPtr matdat;
+        public float lossyScaleX, lossyScaleY, lossyScaleZ;
+    }
+
+    /// tt_object_build_info (48 bytes): what AssetManager needs to place a device-built object in a scene.
+    [StructLayout(LayoutKind.Sequential)]
+    public struct TTObjectBuildInfo
+    {
+        public uint nNodes, nTris, bvh2Depth, maxMatDat;
+        public float aabbMinX, aabbMinY, aabbMinZ, aabbMaxX, aabbMaxY, aabbMaxZ;
+        public uint presortedOnHost, pad;
+    }
+
     /// A ParentObject's BLAS resident on a GPU (tt_object): created once (TrueTraceHipTracer.CreateObject),
     /// assembled into any number of scenes on its device, and free to be disposed once an assembly has returned.
     public sealed class TrueTraceHipObject : IDisposable
@@ -744,6 +785,18 @@ namespace TrueTrace.Hip
                 var st = Native.tt_object_get_info(m_obj, out TTObjectInfo info);
                 if (st != TTStatus.Ok) throw new InvalidOperationException($"tt_object_get_info: {st}");
                 return info;
+            }
+        }
+
+        /// CWBVHIndicesBufferInverted on the device (device-built objects only): tt_blas_refit's leaf_of_triangle
+        /// with TTTraceFlags.DevicePtrs.
+        public IntPtr LeafOrderDevice
+        {
+            get
+            {
+                var st = Native.tt_object_leaf_order_device(m_obj, out IntPtr p);
+                if (st != TTStatus.Ok) throw new InvalidOperationException($"tt_object_leaf_order_device: {st}");
+                return p;
             }
         }
 

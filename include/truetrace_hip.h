@@ -296,6 +296,57 @@ tt_status tt_object_create(tt_ctx* ctx, const tt_cwbvh_node* nodes, uint32_t n_n
 tt_status tt_object_get_info(const tt_object* obj, tt_object_info* info);
 tt_status tt_object_destroy(tt_object* obj);
 
+/* One ParentObject's merged object-space mesh (ParentObject.LoadData output). */
+typedef struct tt_mesh_input {
+    const float* positions;   /* float3 per vertex, object space                          */
+    uint32_t n_vertices;
+    const float* normals;     /* float3 per vertex, nullable -> (0,1,0)                     */
+    const float* tangents;    /* float4 per vertex, nullable -> (1,0,0,1)                   */
+    const float* uvs;         /* float2 per vertex, nullable -> (0,0)                       */
+    const int32_t* indices;   /* Unity index list, 3 per triangle                           */
+    uint32_t n_indices;
+    const int32_t* matdat;    /* per triangle MatDat (submesh material), nullable -> 0       */
+    float lossy_scale[3];     /* transform.lossyScale: AABB padding 0.001/scale (:462-463)  */
+} tt_mesh_input;
+
+/* What a host needs to place a device-built object in a scene (tt_scene_assemble_tlas in truetrace_scene.h). */
+typedef struct tt_object_build_info {
+    uint32_t n_nodes, n_tris, bvh2_depth, max_matdat;
+    float aabb_min[3], aabb_max[3];     /* aabb_untransformed, as tt_blas_info reports it */
+    uint32_t presorted_on_host;         /* 1 when the caller's presort was used */
+    uint32_t pad;
+} tt_object_build_info;
+TT_STATIC_ASSERT(sizeof(tt_object_build_info) == 48, "tt_object_build_info is 48 bytes");
+
+/* A mesh built into a tt_object on ctx's device, with no 88-byte record ever in host memory: ParentObject.BuildTotal
+ * (ParentObject.cs:973-1111) as two kernels around the device builder (csrc/tt_object_build.hip). Pass 1 derives
+ * every triangle's {BBMax, BBMin} box (Create / Extend / Validate with 0.001 / lossy_scale) and checks every index
+ * against n_vertices; the three presorts, the BVH2 and the BVH8 stage run as in tt_bvh2_presort_device and
+ * tt_blas_build_device but on device-resident arrays; pass 2 writes the leaf-ordered 88-byte records, the traversal
+ * records and leaf_of_triangle (CWBVHIndicesBufferInverted) straight from the vertices. Nodes, triangles and the
+ * leaf order are byte for byte those of tt_blas_build (truetrace_scene.h) on the same mesh; the object is an
+ * ordinary tt_object with root 0.
+ *   flags: 0, or TT_TRACE_DEVICE_PTRS: every array the mesh names is in HBM on ctx's device (nullable arrays
+ *          stay nullable).
+ *   presorted: a HOST array of 3 x n indices (tt_bvh2_presort), or NULL: the presort runs on the device, which
+ *          declines n <= 16, non-finite centroids and a depth-exhausted partition above 65536: TT_ERR_UNSUPPORTED,
+ *          the reason in tt_last_error, nothing created; the caller retries with tt_blas_prepare_aabbs +
+ *          tt_bvh2_presort.
+ * A bad index, n_indices % 3 != 0 or null positions / indices: TT_ERR_INVALID_ARG before the builder runs. Any
+ * failure frees everything and leaves *out NULL and the context usable. Synchronizes the context stream. With
+ * tt_ctx_set_timing on, the call records five tt_timing_read entries: pass 1, presort, BVH2 + BVH8, pass 2, the
+ * node mirror's copy. */
+tt_status tt_object_build_device(tt_ctx* ctx, const tt_mesh_input* mesh, const int32_t* presorted, uint32_t flags,
+                                 tt_object** out, tt_object_build_info* info);
+/* Copies an object's nodes (n_nodes x 80 B), triangles (n_tris x 88 B) and leaf order (n_tris) back to the host;
+ * each pointer nullable. The leaf order exists on device-built objects only: TT_ERR_INVALID_ARG for it on an
+ * object of tt_object_create (nodes and tris are still copied). Synchronizes the context stream. */
+tt_status tt_object_read(tt_ctx* ctx, const tt_object* obj, tt_cwbvh_node* nodes, tt_cuda_triangle* tris,
+                         int32_t* leaf_of_triangle);
+/* The device array of leaf_of_triangle (n_tris), owned by the object: what tt_blas_refit takes with
+ * TT_TRACE_DEVICE_PTRS. TT_ERR_INVALID_ARG for an object of tt_object_create. */
+tt_status tt_object_leaf_order_device(const tt_object* obj, const int32_t** leaf_of_triangle_dev);
+
 /* AccumulateData's running sums (AssetManager.cs:995, :1133-1136, :1178-1181), host arithmetic only:
  * node_offsets[0] = tlas_region (the reference's 2 * (parents + instances)), tri_offsets[0] = 0, each later
  * offset adds the previous object's counts; the totals are the scene's n_nodes and n_tris. A host writes

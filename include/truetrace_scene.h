@@ -26,18 +26,7 @@
 extern "C" {
 #endif
 
-/* One ParentObject's merged object-space mesh (ParentObject.LoadData output). */
-typedef struct tt_mesh_input {
-    const float* positions;   /* float3 per vertex, object space                          */
-    uint32_t n_vertices;
-    const float* normals;     /* float3 per vertex, nullable -> (0,1,0)                     */
-    const float* tangents;    /* float4 per vertex, nullable -> (1,0,0,1)                   */
-    const float* uvs;         /* float2 per vertex, nullable -> (0,0)                       */
-    const int32_t* indices;   /* Unity index list, 3 per triangle                           */
-    uint32_t n_indices;
-    const int32_t* matdat;    /* per triangle MatDat (submesh material), nullable -> 0       */
-    float lossy_scale[3];     /* transform.lossyScale: AABB padding 0.001/scale (:462-463)  */
-} tt_mesh_input;
+/* tt_mesh_input (one ParentObject's merged object-space mesh) is declared in truetrace_hip.h. */
 
 typedef struct tt_blas tt_blas;
 
@@ -113,6 +102,24 @@ tt_status tt_scene_assemble(const tt_parent_desc* parents, uint32_t n_parents,
                             const tt_parent_desc* instance_parents, uint32_t n_instance_parents,
                             const tt_instance_desc* instances, uint32_t n_instances,
                             tt_scene_build** out);
+/* The TLAS side alone, for a host that holds device-built objects (tt_object_build_device in truetrace_hip.h)
+ * and no tt_blas: every parent and instance parent is described by what tt_object_build_info reports plus its
+ * matrices and material count. The build holds the TLAS-region nodes only (2 * n_mesh of them, no BLAS nodes
+ * and no triangles: tt_scene_build_copy copies that much), TLASBVH8Indices, _MeshData and the mesh AABBs, each
+ * byte-identical to what tt_scene_assemble yields for the same BLASes; tt_scene_build_get_totals gives the
+ * node and triangle counts of the whole layout (what tt_scene_build_info reports after tt_scene_assemble). */
+typedef struct tt_object_desc {
+    uint32_t n_nodes, n_tris;
+    float aabb_min[3], aabb_max[3];   /* aabb_untransformed */
+    float local_to_world[16];         /* instance parents: unused (their instances carry the matrices) */
+    float world_to_local[16];
+    uint32_t material_count;
+} tt_object_desc;
+tt_status tt_scene_assemble_tlas(const tt_object_desc* parents, uint32_t n_parents,
+                                 const tt_object_desc* instance_parents, uint32_t n_instance_parents,
+                                 const tt_instance_desc* instances, uint32_t n_instances,
+                                 tt_scene_build** out);
+tt_status tt_scene_build_get_totals(const tt_scene_build* s, uint32_t* n_nodes_total, uint32_t* n_tris_total);
 tt_status tt_scene_build_get_info(const tt_scene_build* s, tt_scene_build_info* info);
 tt_status tt_scene_build_copy(const tt_scene_build* s, tt_cwbvh_node* nodes,
                               tt_cuda_triangle* tris, int32_t* tlas_indices,

@@ -2,7 +2,14 @@
 """BLAS build times, host vs the GPU stages (row f4's builder half: BVH2 only, BVH2 + BVH8), on the BASELINE meshes:
 C2 Sponza-shaped (262k tris) and C5 San-Miguel-shaped (10M tris). Both builds must be byte-identical
 (nodes, leaf-ordered triangles, leaf order). Usage: build_bench.py [--meshes c2,c5]
-Prints one JSON document (commit under profiles/)."""
+Prints one JSON document (commit under profiles/).
+
+--leg object [--meshes c2,c5,c4] [--repeats 7] [--check] [--out FILE]: a mesh set to GPU-resident objects,
+(a) Blas(mesh, engine=...) + Engine.create_object (host triangle records, four trips over the bus) against
+(b) Engine.build_object (tt_object_build_device); the two alternate, wall-clock to the synchronize, medians and
+ranges of the repeats after one warm-up; (b)'s stage split from the HIP-event entries of tt_timing_read
+(host_walk_and_rest: the wall clock outside them -- the mesh upload, allocations, the host walk). c4 is
+C4's object set: the street plane and 600 props. --check compares what (b) reads back with the host build."""
 import argparse
 import json
 import os
@@ -15,14 +22,119 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "truetrace-unity-pathtracer_amd", "python"))
 
 
+COPY_TBS = 6.29  # the float4 copy rate of profiles/r09/assemble/bench.json, TB/s
+STAGES = ("pass1_boxes", "presort", "bvh2_bvh8", "pass2_records", "mirror_copy")
+
+
+def _stats(xs):
+    return {"median": round(float(np.median(xs)), 3), "min": round(min(xs), 3), "max": round(max(xs), 3)}
+
+
+def _mesh_set(tthip, name):
+    if name == "c2":
+        return [tthip.Mesh.sponza()]
+    if name == "c5":
+        return [tthip.Mesh.san_miguel()]
+    import ttconfigs as T  # C4's object set, as c4_bistro_manager draws it
+
+    rng = np.random.default_rng(T.C4_SEED)
+    sizes = np.exp(rng.uniform(np.log(200), np.log(40000), 600)).astype(np.int64)
+    return [tthip.Mesh.ground(-110.0, 110.0, -110.0, 110.0, 128, 128)] + [
+        tthip.Mesh.prop(T._mix_seed(T.C4_SEED, k), int(sizes[k])) for k in range(600)]
+
+
+def _pass2_bytes(view):
+    """Bytes pass 2 needs per triangle: cwbvh_indices, three indices, three vertices' attributes, MatDat read;
+    the 88-byte record, the 48-byte traversal record and leaf_of written."""
+    per_vertex = 12 + (12 if view.normals else 0) + (16 if view.tangents else 0) + (8 if view.uvs else 0)
+    return 4 + 12 + 3 * per_vertex + (4 if view.matdat else 0) + 136 + 4
+
+
+def object_leg(tthip, eng, a):
+    out = {"tool": "tools/build_bench.py --leg object", "repeats": a.repeats, "host_threads": os.cpu_count(),
+           "float4_copy_TBs": COPY_TBS, "rows": []}
+    for name in a.meshes.split(","):
+        meshes = _mesh_set(tthip, name)
+        tris = sum(m.view().n_indices // 3 for m in meshes)
+        ta, tb = [], []
+        for rep in range(a.repeats + 1):  # the first pair warms up
+            t0 = time.perf_counter()
+            objs = [eng.create_object(tthip.Blas(m, engine=eng)) for m in meshes]
+            eng.sync()
+            t1 = time.perf_counter()
+            del objs
+            objs = [eng.build_object(m) for m in meshes]
+            eng.sync()
+            t2 = time.perf_counter()
+            on_host = sum(o.build_info.presorted_on_host for o in objs)
+            del objs
+            if rep:
+                ta.append((t1 - t0) * 1e3)
+                tb.append((t2 - t1) * 1e3)
+        eng.set_timing(True)  # the stage split of (b): five HIP-event entries per object
+        split = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            ms = []
+            for k in range(0, len(meshes), 50):  # the ring keeps 256 entries: read every 50 objects
+                eng.timing_reset()
+                objs = [eng.build_object(m) for m in meshes[k:k + 50]]
+                ms.append(eng.timing_read())
+                del objs
+            wall = (time.perf_counter() - t0) * 1e3
+            ms = np.concatenate(ms)
+            assert len(ms) == 5 * len(meshes), (len(ms), len(meshes))
+            st = dict(zip(STAGES, ms.reshape(-1, 5).sum(0).tolist()))
+            st["host_walk_and_rest"] = wall - sum(st.values())
+            st["wall"] = wall
+            split.append(st)
+        eng.set_timing(False)
+        stages = {k: round(float(np.median([s[k] for s in split])), 3) for k in split[0]}
+        p2_bytes = sum(_pass2_bytes(m.view()) * (m.view().n_indices // 3) for m in meshes)
+        p2_tbs = p2_bytes / (stages["pass2_records"] * 1e-3) / 1e12
+        sa, sb = _stats(ta), _stats(tb)
+        row = {"set": name, "objects": len(meshes), "tris": tris, "presorted_on_host": on_host,
+               "a_blas_then_create_object_ms": sa, "b_build_object_ms": sb, "a_runs_ms": [round(x, 3) for x in ta],
+               "b_runs_ms": [round(x, 3) for x in tb], "ranges_overlap": not (sb["max"] < sa["min"] or sa["max"] < sb["min"]),
+               "b_faster": sb["max"] < sa["min"], "b_stages_ms": stages, "pass2_bytes": p2_bytes,
+               "pass2_TBs": round(p2_tbs, 3), "pass2_share_of_float4_copy": round(p2_tbs / COPY_TBS, 3)}
+        if a.check:
+            same = True
+            for m in meshes:
+                host, o = tthip.Blas(m), eng.build_object(m)
+                n, t, l = o.read()
+                hn, ht = host.arrays()
+                same = same and n.tobytes() == hn.tobytes() and t.tobytes() == ht.tobytes() and bool(
+                    np.array_equal(l, host.leaf_order())) and o.build_info.bvh2_depth == host.info.bvh2_depth
+                del host, o
+            row["identical_to_host_build"] = same
+        out["rows"].append(row)
+        print(f"[object] {row}", file=sys.stderr, flush=True)
+        del meshes
+    text = json.dumps(out, indent=1)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--meshes", default="c2,c5")
+    ap.add_argument("--leg", default="blas", choices=["blas", "object"])
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--check", action="store_true")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch  # noqa: F401  (binds the HIP runtime first)
     import tthip
 
     eng = tthip.Engine(0)
+    if a.leg == "object":
+        object_leg(tthip, eng, a)
+        eng.close()
+        return
     out = {"tool": "tools/build_bench.py", "host_threads": os.cpu_count(), "rows": []}
     for name in a.meshes.split(","):
         mesh = {"c2": tthip.Mesh.sponza, "c5": tthip.Mesh.san_miguel}[name]()

@@ -16,16 +16,19 @@ namespace tt_asm {
 struct ObjectWalk {
     std::vector<uint8_t> reach;  // per node: reached from the root (so valid as a mesh record's root too)
     uint32_t max_matdat = 0;     // largest MatDat of a reachable triangle
+    uint64_t leaf_tris = 0;      // triangles the reached leaves name (a built BLAS names each of its n once)
     std::string why;
 };
 
 // Validator::walk at BLAS level with NodeOffset = TriOffset = 0 (IntersectBVH's index arithmetic,
 // IntersectionKernels.compute:157-213), bounded by the object's own counts: stricter than the whole-scene
-// check, where a BLAS may reach into its neighbours.
+// check, where a BLAS may reach into its neighbours. tris == nullptr (the triangles exist on the device only,
+// tt_object_build_device): every index is checked as before, max_matdat is left at 0 for the caller to supply.
 inline bool walk_object(const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_cuda_triangle* tris, uint32_t n_tris,
                         uint32_t root, ObjectWalk& w) {
     w.reach.assign(n_nodes, 0u);
     w.max_matdat = 0;
+    w.leaf_tris = 0;
     if (root >= n_nodes) {
         w.why = "root " + std::to_string(root) + " outside the object's " + std::to_string(n_nodes) + " nodes";
         return false;
@@ -68,7 +71,8 @@ inline bool walk_object(const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_c
                                 " outside the object's " + std::to_string(n_tris) + " triangles";
                         return false;
                     }
-                    if (tris[t].MatDat > w.max_matdat) w.max_matdat = tris[t].MatDat;
+                    w.leaf_tris++;
+                    if (tris && tris[t].MatDat > w.max_matdat) w.max_matdat = tris[t].MatDat;
                 }
             }
         }

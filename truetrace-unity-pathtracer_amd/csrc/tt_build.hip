@@ -28,11 +28,13 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "tt_build.h"
 #include "tt_ctx.h"
 
 namespace {
 thread_local char g_err[256];  // the failing step of the current build, for tt_last_error
 }
+const char* tt_build_error() { return g_err; }
 
 namespace {
 
@@ -876,6 +878,12 @@ __global__ void k_centroids(int n, const Box* __restrict__ prims, float* __restr
     }
 }
 
+// the three root partitions: position p of the 3n-long index array belongs to axis p / n
+__global__ void k_part_of_axis(int n3, int n, int* __restrict__ part) {
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p < n3) part[p] = p / n;
+}
+
 // exclusive-scan input: live children per segment (0 past the last segment, so base[S] = total)
 struct NextCount {
     const SplitOut* so;
@@ -906,17 +914,17 @@ struct Bvh2Dev {
     uint32_t depth = 0;
 };
 
-static tt_status bvh2_stage(hipStream_t st, const float* aabbs, int n, const int32_t* presorted, Bvh2Dev& R) {
+// position i -> Extend(identity, primitive i): what the sequential union makes of one box
+struct RootBox {
+    const Box* prims;
+    __device__ Box operator()(int i) const { return ExtendOp()(box_init(), prims[i]); }
+};
+__global__ void k_root_of_one(const Box* __restrict__ prims, Box* __restrict__ node_box) {
+    node_box[0] = RootBox{prims}(0);
+}
 
-    // root box: Extend over the primitives in index order (BVH2Builder.cs: BVH2Nodes[0].aabb)
-    Box root = box_init();
-    for (int i = 0; i < n; i++) {
-        const float* b = aabbs + 6 * (size_t)i;
-        for (int k = 0; k < 3; k++) {
-            if (b[3 + k] < root.mn[k]) root.mn[k] = b[3 + k];
-            if (b[k] > root.mx[k]) root.mx[k] = b[k];
-        }
-    }
+// prims (n boxes) and presorted (3 x n) are device arrays; everything the stage makes stays on the device.
+static tt_status bvh2_stage(hipStream_t st, const Box* prims_p, int n, const int32_t* presorted, Bvh2Dev& R) {
     const size_t n2 = 2 * (size_t)n;
     uint32_t depth = 0;
     TT_BH(R.box.alloc(n2));
@@ -926,16 +934,17 @@ static tt_status bvh2_stage(hipStream_t st, const float* aabbs, int n, const int
     if (n == 1) {  // BuildRecursive(0, 2, 0, 1, 0): the root is a leaf
         const uint32_t one = 1u;
         TT_BH(hipMemsetAsync(R.box.p, 0, n2 * sizeof(Box), st));
-        TT_BH(hipMemcpyAsync(R.box.p, &root, sizeof(Box), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_root_of_one, dim3(1), dim3(1), 0, st, prims_p, R.box.p);
+        TT_BH(hipGetLastError());
         TT_BH(hipMemsetAsync(R.left.p, 0, n2 * sizeof(int), st));
         TT_BH(hipMemsetAsync(R.count.p, 0, n2 * sizeof(uint32_t), st));
         TT_BH(hipMemcpyAsync(R.count.p, &one, sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        TT_BH(hipMemcpyAsync(R.final_idx.p, presorted, sizeof(int), hipMemcpyHostToDevice, st));
+        TT_BH(hipMemcpyAsync(R.final_idx.p, presorted, sizeof(int), hipMemcpyDeviceToDevice, st));
         TT_BH(hipStreamSynchronize(st));
         R.depth = 0;
         return TT_OK;
     }
-    DBuf<Box> prims, pre, sufr, c_left, c_right;
+    DBuf<Box> pre, sufr, c_left, c_right;
     DBuf<int> idxb[4], seg, lrank, c_pos, dimv, base, err;
     Box* box_p = R.box.p;
     int* nleft_p = R.left.p;
@@ -947,7 +956,6 @@ static tt_status bvh2_stage(hipStream_t st, const float* aabbs, int n, const int
     DBuf<float> c_cost;
     DBuf<int2> child_id;
     const size_t smax = (size_t)n / 2 + 1;  // live segments per level (>= 2 primitives each)
-    TT_BH(prims.alloc(n));
     TT_BH(pre.alloc(n));
     TT_BH(sufr.alloc(n));
     for (auto& b : idxb) TT_BH(b.alloc(n));
@@ -969,11 +977,9 @@ static tt_status bvh2_stage(hipStream_t st, const float* aabbs, int n, const int
     int* idx[3] = {idxb[0].p, idxb[1].p, idxb[2].p};
     int* tmp = idxb[3].p;
     static_assert(sizeof(Box) == 24, "Box is BBMax xyz, BBMin xyz");
-    TT_BH(hipMemcpyAsync(prims.p, aabbs, (size_t)n * sizeof(Box), hipMemcpyHostToDevice, st));
     for (int d = 0; d < 3; d++)
-        TT_BH(hipMemcpyAsync(idx[d], presorted + (size_t)d * n, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+        TT_BH(hipMemcpyAsync(idx[d], presorted + (size_t)d * n, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, st));
     TT_BH(hipMemsetAsync(box_p, 0, n2 * sizeof(Box), st));  // NativeArrayOptions.ClearMemory
-    TT_BH(hipMemcpyAsync(box_p, &root, sizeof(Box), hipMemcpyHostToDevice, st));
     TT_BH(hipMemsetAsync(nleft_p, 0, n2 * sizeof(int), st));
     TT_BH(hipMemsetAsync(ncount_p, 0, n2 * sizeof(uint32_t), st));
     TT_BH(hipMemsetAsync(seg.p, 0, (size_t)n * sizeof(int), st));  // every position in segment 0 (the root)
@@ -986,12 +992,12 @@ static tt_status bvh2_stage(hipStream_t st, const float* aabbs, int n, const int
     size_t tb = 0;
     {
         size_t t1 = 0;
-        auto fwd = rocprim::make_transform_iterator(cnt, FwdBox{idx[0], prims.p, seg.p});
+        auto fwd = rocprim::make_transform_iterator(cnt, FwdBox{idx[0], prims_p, seg.p});
         TT_BH(rocprim::inclusive_scan_by_key(nullptr, t1, seg.p, fwd, pre.p, (size_t)n, ExtendOp(),
                                              rocprim::equal_to<int>(), st));
         tb = std::max(tb, t1);
         auto rk = rocprim::make_transform_iterator(cnt, RevKey{seg.p, n});
-        auto rb = rocprim::make_transform_iterator(cnt, RevBox{idx[0], prims.p, seg.p, n});
+        auto rb = rocprim::make_transform_iterator(cnt, RevBox{idx[0], prims_p, seg.p, n});
         TT_BH(rocprim::inclusive_scan_by_key(nullptr, t1, rk, rb, sufr.p, (size_t)n, ExtendOp(),
                                              rocprim::equal_to<int>(), st));
         tb = std::max(tb, t1);
@@ -1002,9 +1008,21 @@ static tt_status bvh2_stage(hipStream_t st, const float* aabbs, int n, const int
         auto nc = rocprim::make_transform_iterator(cnt, NextCount{so.p, 1});
         TT_BH(rocprim::exclusive_scan(nullptr, t1, nc, base.p, 0, smax + 1, rocprim::plus<int>(), st));
         tb = std::max(tb, t1);
+        auto rb0 = rocprim::make_transform_iterator(cnt, RootBox{prims_p});
+        TT_BH(rocprim::inclusive_scan(nullptr, t1, rb0, pre.p, (size_t)n, ExtendOp(), st));
+        tb = std::max(tb, t1);
     }
     DBuf<unsigned char> tstore;
     TT_BH(tstore.alloc(tb));
+    // root box: Extend over the primitives in index order (BVH2Builder.cs: BVH2Nodes[0].aabb). Extend keeps the
+    // earlier value on ties, so the union is an order-preserving scan with Extend itself; its last element is
+    // the root.
+    {
+        size_t t = tb;
+        auto rb0 = rocprim::make_transform_iterator(cnt, RootBox{prims_p});
+        TT_BH(rocprim::inclusive_scan(tstore.p, t, rb0, pre.p, (size_t)n, ExtendOp(), st));
+        TT_BH(hipMemcpyAsync(box_p, pre.p + (n - 1), sizeof(Box), hipMemcpyDeviceToDevice, st));
+    }
 
     int S = 1;
     while (S > 0) {
@@ -1012,12 +1030,12 @@ static tt_status bvh2_stage(hipStream_t st, const float* aabbs, int n, const int
         TT_BH(hipMemsetAsync(best.p, 0xff, 3 * (size_t)S * sizeof(unsigned long long), st));
         for (int d = 0; d < 3; d++) {
             size_t t = tb;
-            auto fwd = rocprim::make_transform_iterator(cnt, FwdBox{idx[d], prims.p, seg.p});
+            auto fwd = rocprim::make_transform_iterator(cnt, FwdBox{idx[d], prims_p, seg.p});
             TT_BH(rocprim::inclusive_scan_by_key(tstore.p, t, seg.p, fwd, pre.p, (size_t)n, ExtendOp(),
                                                  rocprim::equal_to<int>(), st));
             t = tb;
             auto rk = rocprim::make_transform_iterator(cnt, RevKey{seg.p, n});
-            auto rb = rocprim::make_transform_iterator(cnt, RevBox{idx[d], prims.p, seg.p, n});
+            auto rb = rocprim::make_transform_iterator(cnt, RevBox{idx[d], prims_p, seg.p, n});
             TT_BH(rocprim::inclusive_scan_by_key(tstore.p, t, rk, rb, sufr.p, (size_t)n, ExtendOp(),
                                                  rocprim::equal_to<int>(), st));
             hipLaunchKernelGGL(k_cost, dim3(grid_of(n)), dim3(kBlock), 0, st, n, seg.p, segs.p, pre.p, sufr.p,
@@ -1068,6 +1086,22 @@ static tt_status check_inputs(tt_ctx* ctx, const float* aabbs, uint32_t n, const
     return TT_OK;
 }
 
+// The exported forms take host arrays: copied to the device here, the results copied back below.
+struct DevInputs {
+    DBuf<Box> prims;
+    DBuf<int> pre;
+};
+static tt_status upload_inputs(hipStream_t st, const float* aabbs, uint32_t n, const int32_t* presorted, DevInputs& D) {
+    static_assert(sizeof(Box) == 24, "Box is BBMax xyz, BBMin xyz");
+    TT_BH(D.prims.alloc(n));
+    TT_BH(hipMemcpyAsync(D.prims.p, aabbs, (size_t)n * sizeof(Box), hipMemcpyHostToDevice, st));
+    if (presorted) {
+        TT_BH(D.pre.alloc(3 * (size_t)n));
+        TT_BH(hipMemcpyAsync(D.pre.p, presorted, 3 * (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    return TT_OK;
+}
+
 extern "C" tt_status tt_bvh2_build_device(tt_ctx* ctx, const float* aabbs, uint32_t n, const int32_t* presorted,
                                           int32_t* final_indices, float* node_aabbs, int32_t* node_left,
                                           uint32_t* node_count, uint32_t* max_depth) {
@@ -1075,8 +1109,9 @@ extern "C" tt_status tt_bvh2_build_device(tt_ctx* ctx, const float* aabbs, uint3
     if (s != TT_OK || !final_indices) return s != TT_OK ? s : TT_ERR_INVALID_ARG;
     TT_BH(hipSetDevice(ctx->device));  // allocations and launches on the context's GPU
     hipStream_t st = ctx->stream;
+    DevInputs D;
     Bvh2Dev R;
-    if ((s = bvh2_stage(st, aabbs, (int)n, presorted, R)) != TT_OK) {
+    if ((s = upload_inputs(st, aabbs, n, presorted, D)) != TT_OK || (s = bvh2_stage(st, D.prims.p, (int)n, D.pre.p, R)) != TT_OK) {
         ctx->err = g_err;
         return s;
     }
@@ -1090,29 +1125,49 @@ extern "C" tt_status tt_bvh2_build_device(tt_ctx* ctx, const float* aabbs, uint3
     return TT_OK;
 }
 
-static tt_status blas_device(tt_ctx* ctx, const float* aabbs, uint32_t n, const int32_t* presorted,
-                             tt_cwbvh_node* nodes, uint32_t max_nodes, uint32_t* n_nodes, int32_t* cwbvh_indices,
-                             uint32_t* bvh2_depth);
+static tt_status blas_device(hipStream_t st, const Box* prims, uint32_t n, const int32_t* presorted, tt_blas_dev& out);
 
-extern "C" tt_status tt_blas_build_device(tt_ctx* ctx, const float* aabbs, uint32_t n, const int32_t* presorted,
-                                          tt_cwbvh_node* nodes, uint32_t max_nodes, uint32_t* n_nodes,
-                                          int32_t* cwbvh_indices, uint32_t* bvh2_depth) {
-    g_err[0] = 0;
-    const tt_status s = blas_device(ctx, aabbs, n, presorted, nodes, max_nodes, n_nodes, cwbvh_indices, bvh2_depth);
-    if (s != TT_OK && ctx) ctx->err = g_err[0] ? g_err : "tt_blas_build_device: invalid argument";
-    return s;
-}
-
-static tt_status blas_device(tt_ctx* ctx, const float* aabbs, uint32_t n, const int32_t* presorted,
-                             tt_cwbvh_node* nodes, uint32_t max_nodes, uint32_t* n_nodes, int32_t* cwbvh_indices,
-                             uint32_t* bvh2_depth) {
+static tt_status blas_host_io(tt_ctx* ctx, const float* aabbs, uint32_t n, const int32_t* presorted, tt_cwbvh_node* nodes,
+                              uint32_t max_nodes, uint32_t* n_nodes, int32_t* cwbvh_indices, uint32_t* bvh2_depth) {
     tt_status s = check_inputs(ctx, aabbs, n, presorted);
     if (s != TT_OK) return s;
     if (!nodes || !n_nodes || !cwbvh_indices) return TT_ERR_INVALID_ARG;
     TT_BH(hipSetDevice(ctx->device));  // allocations and launches on the context's GPU
     hipStream_t st = ctx->stream;
+    DevInputs D;
+    tt_blas_dev B;
+    if ((s = upload_inputs(st, aabbs, n, presorted, D)) != TT_OK) return s;
+    if ((s = blas_device(st, D.prims.p, n, D.pre.p, B)) != TT_OK) return s;
+    if (B.n_nodes > max_nodes) TT_BFAIL(TT_ERR_INVALID_ARG, "tt_blas_build_device: max_nodes too small");
+    TT_BH(hipMemcpyAsync(nodes, B.nodes.p, (size_t)B.n_nodes * sizeof(tt_cwbvh_node), hipMemcpyDeviceToHost, st));
+    TT_BH(hipMemcpyAsync(cwbvh_indices, B.cwbvh_indices.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    TT_BH(hipStreamSynchronize(st));
+    *n_nodes = B.n_nodes;
+    if (bvh2_depth) *bvh2_depth = B.bvh2_depth;
+    return TT_OK;
+}
+
+extern "C" tt_status tt_blas_build_device(tt_ctx* ctx, const float* aabbs, uint32_t n, const int32_t* presorted,
+                                          tt_cwbvh_node* nodes, uint32_t max_nodes, uint32_t* n_nodes,
+                                          int32_t* cwbvh_indices, uint32_t* bvh2_depth) {
+    g_err[0] = 0;
+    const tt_status s = blas_host_io(ctx, aabbs, n, presorted, nodes, max_nodes, n_nodes, cwbvh_indices, bvh2_depth);
+    if (s != TT_OK && ctx) ctx->err = g_err[0] ? g_err : "tt_blas_build_device: invalid argument";
+    return s;
+}
+
+tt_status tt_build_blas_dev(hipStream_t st, const float* aabbs_dev, uint32_t n, const int32_t* presorted_dev,
+                            tt_blas_dev& out) {
+    g_err[0] = 0;
+    return blas_device(st, reinterpret_cast<const Box*>(aabbs_dev), n, presorted_dev, out);
+}
+
+// BVH2 + BVH8 + Aggregate over device-resident boxes and presorted lists; the nodes, cwbvh_indices and the root
+// box (the BVH2's node 0) stay on the device.
+static tt_status blas_device(hipStream_t st, const Box* prims, uint32_t n, const int32_t* presorted, tt_blas_dev& out) {
+    tt_status s;
     Bvh2Dev B;
-    if ((s = bvh2_stage(st, aabbs, (int)n, presorted, B)) != TT_OK) return s;
+    if ((s = bvh2_stage(st, prims, (int)n, presorted, B)) != TT_OK) return s;
     const size_t n2 = 2 * (size_t)n;
     // BVH2 levels, root first (for the bottom-up cost pass)
     DBuf<int> order, cnt1, err;
@@ -1176,7 +1231,6 @@ static tt_status blas_device(tt_ctx* ctx, const float* aabbs, uint32_t n, const 
         r8.push_back(h[0]);
     }
     const int total = r8.back();
-    if ((uint32_t)total > max_nodes) TT_BFAIL(TT_ERR_INVALID_ARG, "tt_blas_build_device: max_nodes too small");
     for (size_t L = r8.size() - 1; L-- > 0;) {
         const int lo = r8[L], hi = r8[L + 1];
         if (hi > lo) hipLaunchKernelGGL(k_up8, dim3(grid_of(hi - lo)), dim3(kBlock), 0, st, lo, hi, rec.p);
@@ -1185,40 +1239,36 @@ static tt_status blas_device(tt_ctx* ctx, const float* aabbs, uint32_t n, const 
         const int lo = r8[L], hi = r8[L + 1];
         if (hi > lo) hipLaunchKernelGGL(k_down8, dim3(grid_of(hi - lo)), dim3(kBlock), 0, st, lo, hi, rec.p);
     }
-    DBuf<tt_cwbvh_node> out;
-    DBuf<int> idxo;
-    TT_BH(out.alloc((size_t)total));
-    TT_BH(idxo.alloc(n));
-    TT_BH(hipMemsetAsync(out.p, 0, (size_t)total * sizeof(tt_cwbvh_node), st));
-    TT_BH(hipMemsetAsync(idxo.p, 0, (size_t)n * sizeof(int), st));
+    TT_BH(out.nodes.alloc((size_t)total));
+    TT_BH(out.cwbvh_indices.alloc(n));
+    TT_BH(hipMemsetAsync(out.nodes.p, 0, (size_t)total * sizeof(tt_cwbvh_node), st));
+    TT_BH(hipMemsetAsync(out.cwbvh_indices.p, 0, (size_t)n * sizeof(int), st));
     hipLaunchKernelGGL(k_fill8, dim3(grid_of(total)), dim3(kBlock), 0, st, total, rec.p, B.box.p, dec.p, nprim.p,
-                       firstpos.p, B.final_idx.p, out.p, idxo.p, err.p);
+                       firstpos.p, B.final_idx.p, out.nodes.p, out.cwbvh_indices.p, err.p);
     TT_BH(hipGetLastError());
     int e = 0;
     TT_BH(hipMemcpyAsync(&e, err.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    TT_BH(hipMemcpyAsync(nodes, out.p, (size_t)total * sizeof(tt_cwbvh_node), hipMemcpyDeviceToHost, st));
-    TT_BH(hipMemcpyAsync(cwbvh_indices, idxo.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    TT_BH(hipMemcpyAsync(out.root_box, B.box.p, sizeof(Box), hipMemcpyDeviceToHost, st));
     TT_BH(hipStreamSynchronize(st));
     if (e) TT_BFAIL(TT_ERR_UNSUPPORTED, "BVH8 stage: a node's quantization exponent is not a power of two");
-    *n_nodes = (uint32_t)total;
-    if (bvh2_depth) *bvh2_depth = B.depth;
+    out.n_nodes = (uint32_t)total;
+    out.bvh2_depth = B.depth;
     return TT_OK;
 }
 
 // The three presorts of BVH2Builder on the GPU. TT_ERR_UNSUPPORTED (the caller sorts on the host,
 // tt_bvh2_presort) when a key is not finite or a depth-exhausted partition is too large for the
 // one-thread heapsort.
-static tt_status presort_device(hipStream_t st, const float* aabbs, int n, int32_t* presorted) {
+// prims (n boxes) and presorted (3 x n, the output) are device arrays.
+static tt_status presort_device(hipStream_t st, const Box* prims_p, int n, int32_t* presorted) {
     const int n3 = 3 * n;
-    DBuf<Box> prims;
     DBuf<float> cent;
-    DBuf<int> it, part, gerank, lerank, alist, blist, pk, cnt, err;
+    int* const it_p = presorted;  // sorted in place
+    DBuf<int> part, gerank, lerank, alist, blist, pk, cnt, err;
     DBuf<SortPart> parts, next;
     DBuf<int2> res, child;
     const size_t pmax = (size_t)n3 / 17 + 4;  // live partitions per level (> 16 elements each)
-    TT_BH(prims.alloc(n));
     TT_BH(cent.alloc(n3));
-    TT_BH(it.alloc(n3));
     TT_BH(part.alloc(n3));
     TT_BH(gerank.alloc(n3));
     TT_BH(lerank.alloc(n3));
@@ -1231,9 +1281,8 @@ static tt_status presort_device(hipStream_t st, const float* aabbs, int n, int32
     TT_BH(child.alloc(pmax));
     TT_BH(cnt.alloc(1));
     TT_BH(err.alloc(1));
-    TT_BH(hipMemcpyAsync(prims.p, aabbs, (size_t)n * sizeof(Box), hipMemcpyHostToDevice, st));
     TT_BH(hipMemsetAsync(err.p, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_centroids, dim3(grid_of(n)), dim3(kBlock), 0, st, n, prims.p, cent.p, it.p, err.p);
+    hipLaunchKernelGGL(k_centroids, dim3(grid_of(n)), dim3(kBlock), 0, st, n, prims_p, cent.p, it_p, err.p);
     int bad = 0;
     TT_BH(hipMemcpyAsync(&bad, err.p, sizeof(int), hipMemcpyDeviceToHost, st));
     TT_BH(hipStreamSynchronize(st));
@@ -1243,21 +1292,18 @@ static tt_status presort_device(hipStream_t st, const float* aabbs, int n, int32
     int fl = 0;
     for (int m = n; m >= 1; m /= 2) fl++;
     std::vector<SortPart> roots;
-    std::vector<int> part_h(n3, -1);
     for (int d = 0; d < 3; d++) roots.push_back(SortPart{d * n, d * n + n - 1, 2 * fl});
     int P = (int)roots.size();
-    for (int s = 0; s < P; s++)
-        for (int p = roots[s].lo; p <= roots[s].hi; p++) part_h[p] = s;
     TT_BH(hipMemcpyAsync(parts.p, roots.data(), (size_t)P * sizeof(SortPart), hipMemcpyHostToDevice, st));
-    TT_BH(hipMemcpyAsync(part.p, part_h.data(), (size_t)n3 * sizeof(int), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_part_of_axis, dim3(grid_of(n3)), dim3(kBlock), 0, st, n3, n, part.p);
     auto cnt_it = rocprim::make_counting_iterator<int>(0);
     size_t tb = 0, t1 = 0;
     {
-        auto ge = rocprim::make_transform_iterator(cnt_it, GeFlag{it.p, part.p, parts.p, pk.p, cent.p, n});
+        auto ge = rocprim::make_transform_iterator(cnt_it, GeFlag{it_p, part.p, parts.p, pk.p, cent.p, n});
         TT_BH(rocprim::exclusive_scan_by_key(nullptr, t1, part.p, ge, gerank.p, 0, (size_t)n3, rocprim::plus<int>(),
                                              rocprim::equal_to<int>(), st));
         tb = std::max(tb, t1);
-        auto le = rocprim::make_transform_iterator(cnt_it, LeFlagRev{it.p, part.p, parts.p, pk.p, cent.p, n, n3});
+        auto le = rocprim::make_transform_iterator(cnt_it, LeFlagRev{it_p, part.p, parts.p, pk.p, cent.p, n, n3});
         auto rk = rocprim::make_transform_iterator(cnt_it, PartKeyRev{part.p, n3});
         TT_BH(rocprim::exclusive_scan_by_key(nullptr, t1, rk, le, lerank.p, 0, (size_t)n3, rocprim::plus<int>(),
                                              rocprim::equal_to<int>(), st));
@@ -1266,24 +1312,24 @@ static tt_status presort_device(hipStream_t st, const float* aabbs, int n, int32
     DBuf<unsigned char> tstore;
     TT_BH(tstore.alloc(tb));
     while (P > 0) {
-        hipLaunchKernelGGL(k_pivot, dim3(grid_of(P)), dim3(kBlock), 0, st, P, parts.p, it.p, cent.p, n, pk.p);
+        hipLaunchKernelGGL(k_pivot, dim3(grid_of(P)), dim3(kBlock), 0, st, P, parts.p, it_p, cent.p, n, pk.p);
         size_t t = tb;
-        auto ge = rocprim::make_transform_iterator(cnt_it, GeFlag{it.p, part.p, parts.p, pk.p, cent.p, n});
+        auto ge = rocprim::make_transform_iterator(cnt_it, GeFlag{it_p, part.p, parts.p, pk.p, cent.p, n});
         TT_BH(rocprim::exclusive_scan_by_key(tstore.p, t, part.p, ge, gerank.p, 0, (size_t)n3, rocprim::plus<int>(),
                                              rocprim::equal_to<int>(), st));
         t = tb;
-        auto le = rocprim::make_transform_iterator(cnt_it, LeFlagRev{it.p, part.p, parts.p, pk.p, cent.p, n, n3});
+        auto le = rocprim::make_transform_iterator(cnt_it, LeFlagRev{it_p, part.p, parts.p, pk.p, cent.p, n, n3});
         auto rk = rocprim::make_transform_iterator(cnt_it, PartKeyRev{part.p, n3});
         TT_BH(rocprim::exclusive_scan_by_key(tstore.p, t, rk, le, lerank.p, 0, (size_t)n3, rocprim::plus<int>(),
                                              rocprim::equal_to<int>(), st));
-        hipLaunchKernelGGL(k_stops, dim3(grid_of(n3)), dim3(kBlock), 0, st, n3, part.p, parts.p, it.p, pk.p, cent.p, n,
+        hipLaunchKernelGGL(k_stops, dim3(grid_of(n3)), dim3(kBlock), 0, st, n3, part.p, parts.p, it_p, pk.p, cent.p, n,
                            gerank.p, lerank.p, alist.p, blist.p);
         hipLaunchKernelGGL(k_crossing, dim3(grid_of(P)), dim3(kBlock), 0, st, P, parts.p, gerank.p, lerank.p, alist.p,
                            blist.p, n3, res.p);
         hipLaunchKernelGGL(k_pswap, dim3(grid_of(n3)), dim3(kBlock), 0, st, n3, part.p, parts.p, res.p, alist.p, blist.p,
-                           it.p);
+                           it_p);
         TT_BH(hipMemsetAsync(cnt.p, 0, sizeof(int), st));
-        hipLaunchKernelGGL(k_children_sort, dim3(grid_of(P)), dim3(kBlock), 0, st, P, parts.p, res.p, it.p, cent.p, n,
+        hipLaunchKernelGGL(k_children_sort, dim3(grid_of(P)), dim3(kBlock), 0, st, P, parts.p, res.p, it_p, cent.p, n,
                            next.p, cnt.p, child.p, err.p);
         hipLaunchKernelGGL(k_repart, dim3(grid_of(n3)), dim3(kBlock), 0, st, n3, part.p, res.p, child.p);
         TT_BH(hipGetLastError());
@@ -1296,9 +1342,13 @@ static tt_status presort_device(hipStream_t st, const float* aabbs, int n, int32
         std::swap(parts.p, next.p);
         P = h[0];
     }
-    TT_BH(hipMemcpyAsync(presorted, it.p, (size_t)n3 * sizeof(int), hipMemcpyDeviceToHost, st));
-    TT_BH(hipStreamSynchronize(st));
     return TT_OK;
+}
+
+tt_status tt_build_presort_dev(hipStream_t st, const float* aabbs_dev, uint32_t n, int32_t* presorted_dev) {
+    g_err[0] = 0;
+    if (n >= (1u << 29)) TT_BFAIL(TT_ERR_INVALID_ARG, "presort: too many primitives");
+    return presort_device(st, reinterpret_cast<const Box*>(aabbs_dev), (int)n, presorted_dev);
 }
 
 extern "C" tt_status tt_bvh2_presort_device(tt_ctx* ctx, const float* aabbs, uint32_t n, int32_t* presorted) {
@@ -1308,7 +1358,18 @@ extern "C" tt_status tt_bvh2_presort_device(tt_ctx* ctx, const float* aabbs, uin
         ctx->err = "tt_bvh2_presort_device: hipSetDevice failed";
         return TT_ERR_HIP;
     }
-    const tt_status s = presort_device(ctx->stream, aabbs, (int)n, presorted);
+    auto run = [&]() -> tt_status {
+        hipStream_t st = ctx->stream;
+        DevInputs D;
+        tt_status s = upload_inputs(st, aabbs, n, nullptr, D);
+        if (s != TT_OK) return s;
+        TT_BH(D.pre.alloc(3 * (size_t)n));
+        if ((s = presort_device(st, D.prims.p, (int)n, D.pre.p)) != TT_OK) return s;
+        TT_BH(hipMemcpyAsync(presorted, D.pre.p, 3 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+        TT_BH(hipStreamSynchronize(st));
+        return TT_OK;
+    };
+    const tt_status s = run();
     if (s != TT_OK) ctx->err = g_err[0] ? g_err : "tt_bvh2_presort_device failed";
     return s;
 }

@@ -303,6 +303,10 @@ struct tt_object {
     DevBuf<TriPos> d_tripos;          // derived once, on the GPU
     std::vector<tt_cwbvh_node> nodes;  // host mirror: an assembled scene's host.nodes is composed from these
     tt_asm::ObjectWalk walk;           // the nodes the BLAS walk reached, the largest MatDat it saw
+    // tt_object_build_device only: CWBVHIndicesBufferInverted (source triangle -> leaf position) and the summary
+    bool built = false;
+    DevBuf<int32_t> d_leaf_of;
+    tt_object_build_info build_info{};
 };
 
 // Scene-mutating calls are refused on a borrower (update the lender), and reallocating ones on a

@@ -767,6 +767,7 @@ struct tt_scene_build {
     std::vector<tt_mesh_data> meshdata;
     std::vector<float> mesh_aabbs;  // MeshAABBs, n_mesh x {BBMax, BBMin}
     uint32_t tlas_nodes = 0;
+    uint32_t n_nodes_total = 0, n_tris_total = 0;  // the whole layout's (a TLAS-only build holds fewer nodes)
 };
 
 extern "C" {
@@ -1181,6 +1182,113 @@ static AABB transformed_aabb(const AABB& a, const float* l2w) {
     return o;
 }
 
+// The TLAS side of AccumulateData / UpdateTLAS / ConstructNewTLAS, from per-object summaries alone: the layout's
+// running sums, _MeshData, MeshAABBs, and the TLAS over them written into s->nodes[0, 2 * n_mesh). Shared by
+// tt_scene_assemble (which then copies the BLASes behind it) and tt_scene_assemble_tlas (which has none to copy).
+// node_at / tri_at (parents, then instance parents): where each object's nodes and triangles go. s->nodes is
+// sized here: the whole layout's nodes (zeroed) with `whole`, else the TLAS region alone.
+static tt_status assemble_tlas_side(const tt_object_desc* parents, uint32_t n_parents, const tt_object_desc* iparents,
+                                    uint32_t n_iparents, const tt_instance_desc* instances, uint32_t n_instances,
+                                    bool whole, tt_scene_build* s, std::vector<int32_t>& node_at,
+                                    std::vector<int32_t>& tri_at) {
+    const uint32_t n_mesh = n_parents + n_instances;
+    // AccumulateData (AssetManager.cs:994-1185): TLAS slots 2*(P+I), then parents, then
+    // instance parents, node and triangle buffers concatenated in that order.
+    uint64_t node_total = 2ull * n_mesh, tri_total = 0;
+    for (uint32_t i = 0; i < n_parents; i++) { node_total += parents[i].n_nodes; tri_total += parents[i].n_tris; }
+    for (uint32_t i = 0; i < n_iparents; i++) { node_total += iparents[i].n_nodes; tri_total += iparents[i].n_tris; }
+    if (node_total > 0x7fffffffull || tri_total > 0x7fffffffull) return TT_ERR_UNSUPPORTED;
+    s->n_nodes_total = (uint32_t)node_total;
+    s->n_tris_total = (uint32_t)tri_total;
+    tt_cwbvh_node zero_node;
+    std::memset(&zero_node, 0, sizeof(zero_node));
+    s->nodes.assign(whole ? (size_t)node_total : 2 * (size_t)n_mesh, zero_node);
+    auto box_of = [](const tt_object_desc& d) {
+        AABB a;
+        a.BBMin = v3(d.aabb_min[0], d.aabb_min[1], d.aabb_min[2]);
+        a.BBMax = v3(d.aabb_max[0], d.aabb_max[1], d.aabb_max[2]);
+        return a;
+    };
+
+    // UpdateTLAS (:1655-1750): MyMeshDataCompacted per parent, per instance.
+    std::vector<AABB> MeshAABBs(n_mesh);
+    int32_t aggregated_bvh_node_count = (int32_t)(2 * n_mesh);
+    int32_t AggTriCount = 0, MatOffset = 0;
+    s->meshdata.resize(n_mesh);
+    node_at.clear();
+    tri_at.clear();
+    for (uint32_t i = 0; i < n_parents; i++) {
+        node_at.push_back(aggregated_bvh_node_count);
+        tri_at.push_back(AggTriCount);
+        tt_mesh_data& md = s->meshdata[i];
+        std::memset(&md, 0, sizeof(md));
+        std::memcpy(md.W2L, parents[i].world_to_local, sizeof(md.W2L));
+        md.TriOffset = AggTriCount;
+        md.NodeOffset = aggregated_bvh_node_count;
+        md.MaterialOffset = MatOffset;
+        md.mesh_data_bvh_offsets = aggregated_bvh_node_count;
+        MatOffset += (int32_t)parents[i].material_count;
+        MeshAABBs[i] = transformed_aabb(box_of(parents[i]), parents[i].local_to_world);
+        aggregated_bvh_node_count += (int32_t)parents[i].n_nodes;
+        AggTriCount += (int32_t)parents[i].n_tris;
+    }
+    struct Agg { int32_t tri, node, mat, root; };
+    std::vector<Agg> aggs(n_iparents);
+    for (uint32_t i = 0; i < n_iparents; i++) {
+        node_at.push_back(aggregated_bvh_node_count);
+        tri_at.push_back(AggTriCount);
+        aggs[i] = Agg{AggTriCount, aggregated_bvh_node_count, MatOffset, aggregated_bvh_node_count};
+        MatOffset += (int32_t)iparents[i].material_count;
+        aggregated_bvh_node_count += (int32_t)iparents[i].n_nodes;
+        AggTriCount += (int32_t)iparents[i].n_tris;
+    }
+    for (uint32_t i = 0; i < n_instances; i++) {
+        const Agg& a = aggs[instances[i].instance_parent];
+        tt_mesh_data& md = s->meshdata[n_parents + i];
+        std::memset(&md, 0, sizeof(md));
+        std::memcpy(md.W2L, instances[i].world_to_local, sizeof(md.W2L));
+        md.TriOffset = a.tri;
+        md.NodeOffset = a.node;
+        md.MaterialOffset = a.mat;
+        md.mesh_data_bvh_offsets = a.root;
+        MeshAABBs[n_parents + i] = transformed_aabb(box_of(iparents[instances[i].instance_parent]), instances[i].local_to_world);
+    }
+
+    // ConstructNewTLAS (:1350-1356, :1411-1412): BVH2 over mesh AABBs, BVH8, Aggregate.
+    bool ok = false;
+    BVH2Builder bvh2;
+    BVH8Builder bvh8;
+    run_big_stack([&] {
+        bvh2.build(MeshAABBs.data(), (int)n_mesh);
+        ok = bvh8.build(bvh2);
+    });
+    if (!ok || bvh8.BVH8Nodes.size() > 2ull * n_mesh) return TT_ERR_UNSUPPORTED;
+    Aggregate(bvh8.BVH8Nodes, s->nodes.data());
+    s->tlas_nodes = (uint32_t)bvh8.BVH8Nodes.size();
+    s->mesh_aabbs.resize(6 * (size_t)n_mesh);
+    for (uint32_t i = 0; i < n_mesh; i++) {
+        const AABB& b = MeshAABBs[i];
+        const float v[6] = {b.BBMax.x, b.BBMax.y, b.BBMax.z, b.BBMin.x, b.BBMin.y, b.BBMin.z};
+        std::memcpy(&s->mesh_aabbs[6 * (size_t)i], v, sizeof(v));
+    }
+    s->tlas_indices.assign(bvh8.cwbvh_indices.begin(), bvh8.cwbvh_indices.end());
+    return TT_OK;
+}
+
+static tt_object_desc desc_of(const tt_parent_desc& p) {
+    tt_object_desc d;
+    std::memset(&d, 0, sizeof(d));
+    d.n_nodes = (uint32_t)p.blas->nodes.size();
+    d.n_tris = (uint32_t)p.blas->tris.size();
+    const AABB& a = p.blas->aabb_untransformed;
+    d.aabb_min[0] = a.BBMin.x; d.aabb_min[1] = a.BBMin.y; d.aabb_min[2] = a.BBMin.z;
+    d.aabb_max[0] = a.BBMax.x; d.aabb_max[1] = a.BBMax.y; d.aabb_max[2] = a.BBMax.z;
+    std::memcpy(d.local_to_world, p.local_to_world, sizeof(d.local_to_world));
+    std::memcpy(d.world_to_local, p.world_to_local, sizeof(d.world_to_local));
+    d.material_count = p.material_count;
+    return d;
+}
+
 tt_status tt_scene_assemble(const tt_parent_desc* parents, uint32_t n_parents,
                             const tt_parent_desc* iparents, uint32_t n_iparents,
                             const tt_instance_desc* instances, uint32_t n_instances,
@@ -1194,87 +1302,46 @@ tt_status tt_scene_assemble(const tt_parent_desc* parents, uint32_t n_parents,
     for (uint32_t i = 0; i < n_instances; i++) if (instances[i].instance_parent >= n_iparents) return TT_ERR_INVALID_ARG;
     tt_scene_build* s = new (std::nothrow) tt_scene_build();
     if (!s) return TT_ERR_OOM;
-
-    // AccumulateData (AssetManager.cs:994-1185): TLAS slots 2*(P+I), then parents, then
-    // instance parents, node and triangle buffers concatenated in that order.
-    uint64_t node_total = 2ull * n_mesh, tri_total = 0;
-    for (uint32_t i = 0; i < n_parents; i++) { node_total += parents[i].blas->nodes.size(); tri_total += parents[i].blas->tris.size(); }
-    for (uint32_t i = 0; i < n_iparents; i++) { node_total += iparents[i].blas->nodes.size(); tri_total += iparents[i].blas->tris.size(); }
-    if (node_total > 0x7fffffffull || tri_total > 0x7fffffffull) { delete s; return TT_ERR_UNSUPPORTED; }
-    tt_cwbvh_node zero_node;
-    std::memset(&zero_node, 0, sizeof(zero_node));
-    s->nodes.assign((size_t)node_total, zero_node);
-    s->tris.resize((size_t)tri_total);
-
-    // UpdateTLAS (:1655-1750): MyMeshDataCompacted per parent, per instance.
-    std::vector<AABB> MeshAABBs(n_mesh);
-    int32_t aggregated_bvh_node_count = (int32_t)(2 * n_mesh);
-    int32_t AggTriCount = 0, MatOffset = 0;
-    s->meshdata.resize(n_mesh);
-    auto place = [&](const tt_blas* b) {
-        std::memcpy(&s->nodes[(size_t)aggregated_bvh_node_count], b->nodes.data(), b->nodes.size() * sizeof(tt_cwbvh_node));
-        std::memcpy(&s->tris[(size_t)AggTriCount], b->tris.data(), b->tris.size() * sizeof(tt_cuda_triangle));
-    };
-    for (uint32_t i = 0; i < n_parents; i++) {
-        const tt_blas* b = parents[i].blas;
-        place(b);
-        tt_mesh_data& md = s->meshdata[i];
-        std::memset(&md, 0, sizeof(md));
-        std::memcpy(md.W2L, parents[i].world_to_local, sizeof(md.W2L));
-        md.TriOffset = AggTriCount;
-        md.NodeOffset = aggregated_bvh_node_count;
-        md.MaterialOffset = MatOffset;
-        md.mesh_data_bvh_offsets = aggregated_bvh_node_count;
-        MatOffset += (int32_t)parents[i].material_count;
-        MeshAABBs[i] = transformed_aabb(b->aabb_untransformed, parents[i].local_to_world);
-        aggregated_bvh_node_count += (int32_t)b->nodes.size();
-        AggTriCount += (int32_t)b->tris.size();
+    std::vector<tt_object_desc> pd, ipd;
+    for (uint32_t i = 0; i < n_parents; i++) pd.push_back(desc_of(parents[i]));
+    for (uint32_t i = 0; i < n_iparents; i++) ipd.push_back(desc_of(iparents[i]));
+    std::vector<int32_t> node_at, tri_at;
+    const tt_status st = assemble_tlas_side(pd.data(), n_parents, ipd.data(), n_iparents, instances, n_instances, true, s, node_at, tri_at);
+    if (st != TT_OK) { delete s; return st; }
+    s->tris.resize(s->n_tris_total);
+    for (uint32_t i = 0; i < n_parents + n_iparents; i++) {
+        const tt_blas* b = i < n_parents ? parents[i].blas : iparents[i - n_parents].blas;
+        std::memcpy(&s->nodes[(size_t)node_at[i]], b->nodes.data(), b->nodes.size() * sizeof(tt_cwbvh_node));
+        std::memcpy(&s->tris[(size_t)tri_at[i]], b->tris.data(), b->tris.size() * sizeof(tt_cuda_triangle));
     }
-    struct Agg { int32_t tri, node, mat, root; };
-    std::vector<Agg> aggs(n_iparents);
-    for (uint32_t i = 0; i < n_iparents; i++) {
-        const tt_blas* b = iparents[i].blas;
-        place(b);
-        aggs[i] = Agg{AggTriCount, aggregated_bvh_node_count, MatOffset, aggregated_bvh_node_count};
-        MatOffset += (int32_t)iparents[i].material_count;
-        aggregated_bvh_node_count += (int32_t)b->nodes.size();
-        AggTriCount += (int32_t)b->tris.size();
-    }
-    for (uint32_t i = 0; i < n_instances; i++) {
-        const Agg& a = aggs[instances[i].instance_parent];
-        tt_mesh_data& md = s->meshdata[n_parents + i];
-        std::memset(&md, 0, sizeof(md));
-        std::memcpy(md.W2L, instances[i].world_to_local, sizeof(md.W2L));
-        md.TriOffset = a.tri;
-        md.NodeOffset = a.node;
-        md.MaterialOffset = a.mat;
-        md.mesh_data_bvh_offsets = a.root;
-        MeshAABBs[n_parents + i] = transformed_aabb(iparents[instances[i].instance_parent].blas->aabb_untransformed,
-                                                    instances[i].local_to_world);
-    }
-
-    // ConstructNewTLAS (:1350-1356, :1411-1412): BVH2 over mesh AABBs, BVH8, Aggregate.
-    bool ok = false;
-    BVH2Builder bvh2;
-    BVH8Builder bvh8;
-    run_big_stack([&] {
-        bvh2.build(MeshAABBs.data(), (int)n_mesh);
-        ok = bvh8.build(bvh2);
-    });
-    if (!ok || bvh8.BVH8Nodes.size() > 2ull * n_mesh) {
-        delete s;
-        return TT_ERR_UNSUPPORTED;
-    }
-    Aggregate(bvh8.BVH8Nodes, s->nodes.data());
-    s->tlas_nodes = (uint32_t)bvh8.BVH8Nodes.size();
-    s->mesh_aabbs.resize(6 * (size_t)n_mesh);
-    for (uint32_t i = 0; i < n_mesh; i++) {
-        const AABB& b = MeshAABBs[i];
-        const float v[6] = {b.BBMax.x, b.BBMax.y, b.BBMax.z, b.BBMin.x, b.BBMin.y, b.BBMin.z};
-        std::memcpy(&s->mesh_aabbs[6 * (size_t)i], v, sizeof(v));
-    }
-    s->tlas_indices.assign(bvh8.cwbvh_indices.begin(), bvh8.cwbvh_indices.end());
     *out = s;
+    return TT_OK;
+}
+
+tt_status tt_scene_assemble_tlas(const tt_object_desc* parents, uint32_t n_parents,
+                                 const tt_object_desc* iparents, uint32_t n_iparents,
+                                 const tt_instance_desc* instances, uint32_t n_instances,
+                                 tt_scene_build** out) {
+    if (!out || (n_parents && !parents) || (n_iparents && !iparents) || (n_instances && !instances))
+        return TT_ERR_INVALID_ARG;
+    const uint32_t n_mesh = n_parents + n_instances;
+    if (n_mesh == 0) return TT_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < n_parents; i++) if (!parents[i].n_nodes || !parents[i].n_tris) return TT_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < n_iparents; i++) if (!iparents[i].n_nodes || !iparents[i].n_tris) return TT_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < n_instances; i++) if (instances[i].instance_parent >= n_iparents) return TT_ERR_INVALID_ARG;
+    tt_scene_build* s = new (std::nothrow) tt_scene_build();
+    if (!s) return TT_ERR_OOM;
+    std::vector<int32_t> node_at, tri_at;
+    const tt_status st = assemble_tlas_side(parents, n_parents, iparents, n_iparents, instances, n_instances, false, s, node_at, tri_at);
+    if (st != TT_OK) { delete s; return st; }
+    *out = s;
+    return TT_OK;
+}
+
+tt_status tt_scene_build_get_totals(const tt_scene_build* s, uint32_t* n_nodes_total, uint32_t* n_tris_total) {
+    if (!s) return TT_ERR_INVALID_ARG;
+    if (n_nodes_total) *n_nodes_total = s->n_nodes_total;
+    if (n_tris_total) *n_tris_total = s->n_tris_total;
     return TT_OK;
 }
 

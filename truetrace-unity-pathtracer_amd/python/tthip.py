@@ -171,6 +171,17 @@ class ObjectInfo(C.Structure):
                 ("bytes", C.c_uint64)]
 
 
+class ObjectBuildInfo(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint32), ("n_tris", C.c_uint32), ("bvh2_depth", C.c_uint32), ("max_matdat", C.c_uint32),
+                ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3), ("presorted_on_host", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
+class ObjectDesc(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint32), ("n_tris", C.c_uint32), ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3),
+                ("local_to_world", C.c_float * 16), ("world_to_local", C.c_float * 16), ("material_count", C.c_uint32)]
+
+
 class TTError(RuntimeError):
     def __init__(self, status: int, msg: str = ""):
         super().__init__(f"{STATUS_NAMES.get(status, status)}: {msg}")
@@ -205,7 +216,8 @@ HIP_SYMBOLS = ["tt_abi_version", "tt_device_count", "tt_ctx_create", "tt_ctx_des
                "tt_selftest_rcp", "tt_trace_closest_hits", "tt_ctx_share_scene", "tt_scene_upload_terrains",
                "tt_terrain_validate", "tt_trace_heightmap", "tt_trace_heightmap_indirect", "tt_trace_shadow_heightmap",
                "tt_trace_shadow_heightmap_indirect", "tt_object_validate", "tt_object_create", "tt_object_get_info",
-               "tt_object_destroy", "tt_scene_layout_objects", "tt_scene_layout_counts", "tt_scene_assemble_objects"]
+               "tt_object_destroy", "tt_scene_layout_objects", "tt_scene_layout_counts", "tt_scene_assemble_objects",
+               "tt_object_build_device", "tt_object_read", "tt_object_leaf_order_device"]
 SCENE_SYMBOLS = ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_blas_free", "tt_scene_assemble",
                  "tt_scene_build_get_info", "tt_scene_build_copy", "tt_scene_build_free", "tt_pack_octahedral",
                  "tt_bvh2_build", "tt_dotnet_sort_by_key", "tt_synth_cornell", "tt_synth_soup", "tt_synth_sponza",
@@ -213,7 +225,8 @@ SCENE_SYMBOLS = ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_blas_f
                  "tt_synth_mesh_from_arrays", "tt_blas_copy_leaf_order", "tt_blas_prepare_aabbs", "tt_bvh2_presort",
                  "tt_blas_build_from_bvh2", "tt_blas_build_from_cwbvh", "tt_blas_prepare",
                  "tt_blas_build_from_cwbvh_prepared", "tt_blas_prep_free", "tt_terrain_trace_host",
-                 "tt_terrain_trace_detail_host", "tt_terrain_occluded_host", "tt_terrain_normal_host"]
+                 "tt_terrain_trace_detail_host", "tt_terrain_occluded_host", "tt_terrain_normal_host",
+                 "tt_scene_assemble_tlas", "tt_scene_build_get_totals"]
 
 
 def scene_lib():
@@ -232,6 +245,10 @@ def scene_lib():
         L.tt_blas_copy_leaf_order.argtypes = [vp, vp]
         L.tt_blas_copy_leaf_order.restype = i32
         L.tt_scene_assemble.argtypes = [vp, u32, vp, u32, vp, u32, C.POINTER(vp)]
+        L.tt_scene_assemble_tlas.argtypes = [vp, u32, vp, u32, vp, u32, C.POINTER(vp)]
+        L.tt_scene_assemble_tlas.restype = i32
+        L.tt_scene_build_get_totals.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+        L.tt_scene_build_get_totals.restype = i32
         L.tt_scene_build_get_info.argtypes = [vp, C.POINTER(SceneBuildInfo)]
         L.tt_scene_build_copy.argtypes = [vp, vp, vp, vp, vp]
         L.tt_scene_build_free.argtypes = [vp]
@@ -342,6 +359,13 @@ def hip_lib():
             L.tt_scene_assemble_objects.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32]
             for s in ["tt_object_validate", "tt_object_create", "tt_object_get_info", "tt_object_destroy",
                       "tt_scene_layout_objects", "tt_scene_layout_counts", "tt_scene_assemble_objects"]:
+                getattr(L, s).restype = i32
+        if hasattr(L, "tt_object_build_device"):  # (absent from older variant libraries)
+            L.tt_object_build_device.argtypes = [vp, C.POINTER(MeshInput), vp, u32, C.POINTER(vp),
+                                                 C.POINTER(ObjectBuildInfo)]
+            L.tt_object_read.argtypes = [vp, vp, vp, vp, vp]
+            L.tt_object_leaf_order_device.argtypes = [vp, C.POINTER(vp)]
+            for s in ["tt_object_build_device", "tt_object_read", "tt_object_leaf_order_device"]:
                 getattr(L, s).restype = i32
         L.tt_scene_read_nodes.argtypes = [vp, u32, u32, vp]
         L.tt_scene_read_tris.argtypes = [vp, u32, u32, vp]
@@ -575,6 +599,28 @@ class Mesh:
             self.h = None
 
 
+class ArrayMesh:
+    """A mesh over the caller's numpy arrays, every attribute tt_mesh_input names (normals, tangents, uvs and
+    matdat are nullable). Usable wherever a Mesh is built from: Blas(mesh), Engine.build_object(mesh)."""
+
+    def __init__(self, positions, indices, normals=None, tangents=None, uvs=None, matdat=None):
+        def arr(a, dt, width):
+            return None if a is None else np.ascontiguousarray(a, dt).reshape(-1, width)
+
+        self.positions = arr(positions, np.float32, 3)
+        self.indices = np.ascontiguousarray(indices, np.int32).reshape(-1)
+        self.normals, self.tangents, self.uvs = arr(normals, np.float32, 3), arr(tangents, np.float32, 4), arr(uvs, np.float32, 2)
+        self.matdat = None if matdat is None else np.ascontiguousarray(matdat, np.int32).reshape(-1)
+
+    def view(self) -> MeshInput:
+        v = MeshInput(positions=_ptr(self.positions), n_vertices=len(self.positions), normals=_ptr(self.normals),
+                      tangents=_ptr(self.tangents), uvs=_ptr(self.uvs), indices=_ptr(self.indices),
+                      n_indices=self.indices.size, matdat=_ptr(self.matdat))
+        v.lossy_scale[:] = (1.0, 1.0, 1.0)
+        v._owner = self  # the view points into this object's arrays
+        return v
+
+
 _BUILD_ENGINE = None
 _BUILD_MIN_TRIS = 0
 
@@ -742,7 +788,71 @@ class AssetManager:
     def add_instance(self, parent_index: int, local_to_world):
         self.instances.append((parent_index, np.asarray(local_to_world)))
 
+    def add_parent_object(self, obj: "SceneObject", local_to_world=None, materials: Optional[np.ndarray] = None):
+        """add_parent for a device-built object (Engine.build_object): assemble_objects places it by its summary."""
+        assert obj.build_info is not None, "add_parent_object takes an object of Engine.build_object"
+        self.add_parent(obj, local_to_world, materials)
+
+    def add_instance_parent_object(self, obj: "SceneObject", materials: Optional[np.ndarray] = None) -> int:
+        assert obj.build_info is not None, "add_instance_parent_object takes an object of Engine.build_object"
+        return self.add_instance_parent(obj, materials)
+
+    def _instance_descs(self):
+        I = (InstanceDesc * max(1, len(self.instances)))()
+        for i, (pi, l2w) in enumerate(self.instances):
+            I[i].instance_parent = pi
+            I[i].local_to_world[:] = unity_colmajor(l2w)
+            I[i].world_to_local[:] = unity_colmajor(np.linalg.inv(l2w))
+        return I
+
+    def assemble_objects(self, engine: "Engine"):
+        """The scene-change path with no host BLAS anywhere: every parent is a device-built object
+        (add_parent_object / add_instance_parent_object), the TLAS side comes from their summaries
+        (tt_scene_assemble_tlas) and the BLAS side is gathered on the device (Engine.assemble). Returns
+        (Scene, objects); the Scene holds the TLAS-region nodes and no triangles, its meta the layout's totals."""
+        def desc(obj, l2w, nm, d):
+            bi = obj.build_info
+            d.n_nodes, d.n_tris = bi.n_nodes, bi.n_tris
+            d.aabb_min[:], d.aabb_max[:] = bi.aabb_min[:], bi.aabb_max[:]
+            d.local_to_world[:] = unity_colmajor(l2w)
+            d.world_to_local[:] = unity_colmajor(np.linalg.inv(l2w))
+            d.material_count = nm
+
+        P = (ObjectDesc * max(1, len(self.parents)))()
+        for i, (o, l2w, nm) in enumerate(self.parents):
+            desc(o, l2w, nm, P[i])
+        IP = (ObjectDesc * max(1, len(self.instance_parents)))()
+        for i, (o, nm) in enumerate(self.instance_parents):
+            desc(o, np.eye(4), nm, IP[i])
+        I = self._instance_descs()
+        h = C.c_void_p()
+        L = scene_lib()
+        _check(L.tt_scene_assemble_tlas(C.addressof(P), len(self.parents), C.addressof(IP), len(self.instance_parents),
+                                        C.addressof(I), len(self.instances), C.byref(h)), "tt_scene_assemble_tlas")
+        try:
+            info = SceneBuildInfo()
+            L.tt_scene_build_get_info(h, C.byref(info))
+            nodes = np.zeros(info.n_nodes, NODE_DTYPE)
+            tlas = np.zeros(info.n_tlas_indices, np.int32)
+            md = np.zeros(info.n_mesh, MESH_DTYPE)
+            L.tt_scene_build_copy(h, nodes.ctypes.data, None, tlas.ctypes.data, md.ctypes.data)
+            aabbs = np.zeros((info.n_mesh, 6), np.float32)
+            L.tt_scene_build_copy_mesh_aabbs(h, aabbs.ctypes.data)
+            tn, tt = C.c_uint32(), C.c_uint32()
+            L.tt_scene_build_get_totals(h, C.byref(tn), C.byref(tt))
+        finally:
+            L.tt_scene_build_free(h)
+        mats = self.materials + getattr(self, "_ip_mats", [])
+        materials = np.concatenate(mats) if mats else np.zeros(1, MAT_DTYPE)
+        objects = self.blases()
+        engine.assemble(objects, nodes, tlas, md, materials)
+        s = Scene(nodes, np.zeros(0, TRI_DTYPE), tlas, md, materials, tlas_nodes=info.tlas_nodes,
+                  meta={"mesh_aabbs": aabbs, "n_nodes_total": int(tn.value), "n_tris_total": int(tt.value)})
+        return s, objects
+
     def build(self) -> Scene:
+        if not all(isinstance(p[0], Blas) for p in self.parents + self.instance_parents):
+            raise TypeError("AssetManager.build needs host BLASes; device-built objects go through assemble_objects")
         P = (ParentDesc * max(1, len(self.parents)))()
         for i, (b, l2w, nm) in enumerate(self.parents):
             P[i].blas = b.h
@@ -755,11 +865,7 @@ class AssetManager:
             IP[i].local_to_world[:] = unity_colmajor(np.eye(4))
             IP[i].world_to_local[:] = unity_colmajor(np.eye(4))
             IP[i].material_count = nm
-        I = (InstanceDesc * max(1, len(self.instances)))()
-        for i, (pi, l2w) in enumerate(self.instances):
-            I[i].instance_parent = pi
-            I[i].local_to_world[:] = unity_colmajor(l2w)
-            I[i].world_to_local[:] = unity_colmajor(np.linalg.inv(l2w))
+        I = self._instance_descs()
         h = C.c_void_p()
         L = scene_lib()
         st = L.tt_scene_assemble(C.addressof(P), len(self.parents), C.addressof(IP), len(self.instance_parents),
@@ -841,8 +947,28 @@ class SceneObject:
     """tt_object: one BLAS resident on a device (Engine.create_object). An assembly copies it, so it may be
     destroyed as soon as Engine.assemble has returned."""
 
-    def __init__(self, L, handle: int):
+    def __init__(self, L, handle: int, build_info: "ObjectBuildInfo" = None, engine: "Engine" = None):
         self.L, self.h = L, handle
+        self.build_info = build_info  # tt_object_build_info of Engine.build_object, None for create_object
+        self._engine = engine
+
+    def read(self, engine: "Engine" = None):
+        """tt_object_read: (nodes, tris, leaf_of_triangle) copied back from the device. An object of create_object
+        has no leaf order: (nodes, tris, None)."""
+        eng = engine or self._engine
+        info = self.info
+        nodes, tris = np.zeros(info.n_nodes, NODE_DTYPE), np.zeros(info.n_tris, TRI_DTYPE)
+        leaf = np.zeros(info.n_tris, np.int32) if self.build_info is not None else None
+        eng._check(self.L.tt_object_read(eng.h, self.h, _ptr(nodes), _ptr(tris), _ptr(leaf)), "tt_object_read")
+        return nodes, tris, leaf
+
+    @property
+    def leaf_order_device(self) -> int:
+        """tt_object_leaf_order_device: the device address of leaf_of_triangle (n_tris int32), owned by the object;
+        what Engine.blas_refit(..., device=True) takes."""
+        p = C.c_void_p()
+        _check(self.L.tt_object_leaf_order_device(self.h, C.byref(p)), "tt_object_leaf_order_device")
+        return p.value
 
     @property
     def info(self) -> ObjectInfo:
@@ -984,6 +1110,33 @@ class Engine:
         self._check(self.L.tt_object_create(self.h, _ptr(nodes), len(nodes), _ptr(tris), len(tris), int(root),
                                             C.byref(h)), "tt_object_create")
         return SceneObject(self.L, h.value)
+
+    def build_object(self, mesh, lossy_scale=(1.0, 1.0, 1.0), device_arrays: dict = None) -> "SceneObject":
+        """tt_object_build_device: `mesh` (a Mesh or ArrayMesh) built into an object on this engine's device, byte
+        for byte the object create_object(Blas(mesh)) would be, without a host triangle record. device_arrays: device
+        tensors (positions, normals, tangents, uvs, indices, matdat) replacing ALL of the mesh's arrays, passed with
+        TT_TRACE_DEVICE_PTRS (`mesh` then only supplies the counts and the host presort's input). Where the device
+        presort declines (TT_ERR_UNSUPPORTED: n <= 16, non-finite centroids), the host presort is used instead, as
+        Blas(mesh, engine=...) does."""
+        v = mesh.view()
+        v.lossy_scale[:] = lossy_scale
+        host = MeshInput.from_buffer_copy(v)  # the host arrays, for the retry's boxes
+        flags = 0
+        if device_arrays is not None:
+            flags = TT_TRACE_DEVICE_PTRS
+            for k in ("positions", "normals", "tangents", "uvs", "indices", "matdat"):
+                setattr(v, k, _ptr(device_arrays.get(k)))
+        h, info = C.c_void_p(), ObjectBuildInfo()
+        st = self.L.tt_object_build_device(self.h, C.byref(v), None, flags, C.byref(h), C.byref(info))
+        if st == TT_ERR_UNSUPPORTED:
+            S = scene_lib()
+            n = v.n_indices // 3
+            aabbs, pre = np.zeros((n, 6), np.float32), np.zeros((3, n), np.int32)
+            _check(S.tt_blas_prepare_aabbs(C.byref(host), aabbs.ctypes.data), "tt_blas_prepare_aabbs")
+            _check(S.tt_bvh2_presort(aabbs.ctypes.data, n, pre.ctypes.data), "tt_bvh2_presort")
+            st = self.L.tt_object_build_device(self.h, C.byref(v), pre.ctypes.data, flags, C.byref(h), C.byref(info))
+        self._check(st, "tt_object_build_device")
+        return SceneObject(self.L, h.value, build_info=info, engine=self)
 
     def assemble(self, objects, tlas_nodes: np.ndarray, tlas: np.ndarray, meshdata: np.ndarray, materials: np.ndarray):
         """tt_scene_assemble_objects: the scene tt_scene_upload would hold for the host-concatenated arrays, gathered
