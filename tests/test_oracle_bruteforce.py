@@ -1,88 +1,39 @@
-"""An independent check of the oracle and the builder restatement: CWBVH8 traversal must find the
-same closest triangle as a brute-force Moller-Trumbore over every triangle of every instance
-(float64, numpy). Golden fixtures only pin the oracle against itself over time; this pins it
-against geometry. Rays whose answer is numerically fragile in float32 (a hit within 1e-4 of a
-triangle edge, or two candidates within 1e-4 relative in t) are excluded; everything else must
-agree exactly on (mesh, triangle) and to 1e-5 relative in t, and misses must be misses."""
+"""The oracle against geometry: CWBVH8 traversal must give the answers of a float64 brute-force
+Moller-Trumbore over every triangle of every instance (bruteforce.py; numpy, neither nodes nor TLAS read).
+Golden fixtures pin the oracle against itself over time and the GPU parity tests pin the kernels against
+the oracle; this file pins the oracle against truth, for the closest hit under every launch flag and at
+both bounces, for the any-hit loop in both of its modes, and for axis-parallel rays whose slabs are inf / NaN.
+
+A ray whose answer could turn on a float32 rounding is unrobust (bruteforce.py has the predicates) and only
+counted; every other ray must agree exactly on miss / (mesh, triangle) or on occluded / visible, and every
+hit on the reference's triangle must have t and its uv codes within the conditioned bound of
+bruteforce_cases.compare_closest. test_gpu_bruteforce.py makes the same comparison for the kernels."""
+import dataclasses
+import functools
+
 import numpy as np
 import pytest
 
+import bruteforce as BF
+import bruteforce_cases as C
 import oracle_ctypes as O
 import tthip
 
-FAR = 1000.0
+FAR = C.FAR
+THREADS = 4
 
 
-def _brute(sc, origins, dirs, tri_ranges):
-    """Closest hit per ray over all meshes: returns (t, mesh, tri, fragile) as float64 results."""
-    n = len(origins)
-    best_t = np.full(n, np.inf)
-    best_mesh = np.zeros(n, np.int64)
-    best_tri = np.full(n, -1, np.int64)
-    second = np.full(n, np.inf)
-    fragile = np.zeros(n, bool)
-    p0_all = sc.tris["pos0"].astype(np.float64)
-    e1_all = sc.tris["posedge1"].astype(np.float64)
-    e2_all = sc.tris["posedge2"].astype(np.float64)
-    for m, (lo, hi) in enumerate(tri_ranges):
-        W = sc.meshdata["W2L"][m].reshape(4, 4).T.astype(np.float64)  # column-major -> row-major
-        o = origins @ W[:3, :3].T + W[:3, 3]
-        d = dirs @ W[:3, :3].T
-        p0, e1, e2 = p0_all[lo:hi], e1_all[lo:hi], e2_all[lo:hi]
-        for c in range(0, hi - lo, 2048):
-            P0, E1, E2 = p0[c:c + 2048], e1[c:c + 2048], e2[c:c + 2048]
-            h = np.cross(d[:, None, :], E2[None, :, :])
-            a = np.einsum("tk,rtk->rt", E1, h)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                f = 1.0 / a
-                s = o[:, None, :] - P0[None, :, :]
-                u = f * np.einsum("rtk,rtk->rt", s, h)
-                q = np.cross(s, E1[None, :, :])
-                v = f * np.einsum("rk,rtk->rt", d, q)
-                t = f * np.einsum("tk,rtk->rt", E2, q)
-            ok = (u >= 0) & (u <= 1) & (v >= 0) & (u + v <= 1) & (t > 0) & (t < FAR)
-            edge = ok & ((u < 1e-4) | (v < 1e-4) | (u + v > 1 - 1e-4) | (np.abs(a) < 1e-12))
-            tt = np.where(ok, t, np.inf)
-            for r in range(n):  # merge this chunk's candidates into the per-ray top two
-                row = tt[r]
-                k = int(np.argmin(row))
-                if not np.isfinite(row[k]):
-                    continue
-                part = np.partition(row, 1)[:2] if len(row) > 1 else np.array([row[0], np.inf])
-                cand_t, cand_2 = part[0], part[1]
-                if cand_t < best_t[r]:
-                    second[r] = min(best_t[r], cand_2)
-                    best_t[r], best_mesh[r], best_tri[r] = cand_t, m, lo + c + k
-                    fragile[r] = bool(edge[r, k])
-                else:
-                    second[r] = min(second[r], cand_t)
-    with np.errstate(invalid="ignore"):
-        close = np.isfinite(second) & (np.abs(second - best_t) <= 1e-4 * np.maximum(best_t, 1e-6))
-    return best_t, best_mesh, best_tri, fragile | close
-
-
-def _tri_ranges(sc):
-    starts = sorted(set(int(x) for x in sc.meshdata["TriOffset"]))
-    ends = {s: e for s, e in zip(starts, starts[1:] + [len(sc.tris)])}
-    return [(int(t), ends[int(t)]) for t in sc.meshdata["TriOffset"]]
-
-
+# ------------------------------------------------------------------ the cases this file had before the matrix
 def _check(sc, rays, n):
+    """Flags 0, bounce 0, the scene as it is (test_blas_refit.py uses this too)."""
     r = rays.copy()
-    st, _ = O.trace(sc, r, n, 0, FAR, n, 1, nthreads=4)
+    st, _ = O.trace(sc, r, n, 0, FAR, n, 1, nthreads=THREADS)
     assert st == 0
-    o = rays["origin"][:n].astype(np.float64)
-    d = rays["direction"][:n].astype(np.float64)
-    bt, bm, btri, fragile = _brute(sc, o, d, _tri_ranges(sc))
+    ref = C.reference_closest(BF.Geometry.from_scene(sc), rays, n, 0, 0)
     hits = r["hits"][:n]
-    got_t = hits[:, 2].view(np.float32).astype(np.float64)
-    miss = ~np.isfinite(bt)
-    assert np.all(hits[miss, 1] == 0xFFFFFFFF), "oracle hit something brute force misses"
-    robust = ~miss & ~fragile
-    assert robust.sum() > 0.3 * n
-    assert np.array_equal(hits[robust, 1].astype(np.int64), btri[robust]), "different closest triangle"
-    assert np.array_equal(hits[robust, 0].astype(np.int64), bm[robust]), "different mesh"
-    assert np.allclose(got_t[robust], bt[robust], rtol=1e-5, atol=0)
+    assert np.all(hits[~ref.exact, 1] == 0xFFFFFFFF), "oracle hit something brute force misses"
+    assert (ref.robust & ref.hit).sum() > 0.3 * n
+    C.compare_closest(ref, hits, caps=False).check()
 
 
 def _random_rays(rng, n, center, spread):
@@ -124,3 +75,145 @@ def test_sponza_shaped_c2_matches_brute_force():
     rng = np.random.default_rng(3)
     rays = _random_rays(rng, 128, np.array(T.C2_VIEW.position), 1.0)
     _check(sc, rays, 128)
+
+
+# ------------------------------------------------------------------ closest-hit matrix
+N_RAYS = 600
+RAY_SETS = ("random", "axis")
+
+
+@functools.lru_cache(maxsize=None)
+def closest_rays(name, ray_set):
+    g = C.geometry(name)
+    seed = 100 + C.SCENES.index(name)
+    o, d = C.random_rays(g, seed, N_RAYS) if ray_set == "random" else C.axis_rays(g, seed, N_RAYS)
+    return C.ray_buffer(o, d)
+
+
+def oracle_closest(sc, rays, flags, bounce):
+    n = len(rays) // 2
+    r = rays.copy()
+    st, _ = O.trace(sc, r, n, bounce, FAR, n, 1, flags=flags, nthreads=THREADS)
+    assert st == 0
+    other = slice(n, 2 * n) if bounce == 0 else slice(0, n)
+    assert r[other].tobytes() == rays[other].tobytes(), "the other half of the ping-pong buffer was written"
+    return r["hits"][n * bounce:n * bounce + n]
+
+
+@pytest.mark.parametrize("bounce", [0, 1])
+@pytest.mark.parametrize("flags", C.FLAGS)
+@pytest.mark.parametrize("ray_set", RAY_SETS)
+@pytest.mark.parametrize("name", C.SCENES)
+def test_closest_matrix(name, ray_set, flags, bounce):
+    rays = closest_rays(name, ray_set)
+    hits = oracle_closest(C.scene(name), rays, flags, bounce)
+    ref = C.reference_closest(C.geometry(name), rays, len(hits), flags, bounce)
+    C.compare_closest(ref, hits).check()
+
+
+# ------------------------------------------------------------------ any-hit matrix
+SHADOW_SETS = ("random", "axis", "nee")
+# the NEE set needs something between a surface and the light: Cornell's walls and the ground have nothing
+SHADOW_CASES = [(name, s) for name in C.SCENES for s in SHADOW_SETS if s != "nee" or name in ("soup", "instances")]
+
+
+@functools.lru_cache(maxsize=None)
+def shadow_rays(name, ray_set):
+    """(rays, width, height) of a shadow case."""
+    g = C.geometry(name, "shadow")
+    seed = 200 + C.SCENES.index(name)
+    if ray_set == "nee":
+        c2w, ip, light = C.nee_camera(g)
+        frame = O.generate(c2w, ip, C.NEE_W, C.NEE_H, 0.05, FAR)
+        n = C.NEE_W * C.NEE_H
+        assert O.trace(C.scene(name, "shadow"), frame, n, 0, FAR, C.NEE_W, C.NEE_H, nthreads=THREADS)[0] == 0
+        return C.nee_shadow_rays(frame, light, seed), C.NEE_W, C.NEE_H
+    if ray_set == "axis":
+        o, d = C.axis_rays(g, seed, N_RAYS)
+        return C.axis_shadow_buffer(g, o, d, seed), N_RAYS, 1
+    o, d = C.random_rays(g, seed, N_RAYS)
+    return C.shadow_buffer(o, d, seed), N_RAYS, 1
+
+
+def oracle_any_hit(sc, before, W, H, bounce, visibility_check):
+    after = before.copy()
+    vis, col, nee = C.shadow_outputs(len(before), W * H)
+    st, cnt = O.shadow(sc, after, len(after), bounce, W, H, visibility=vis, colors=col, nee_pos=nee, counts=True,
+                       nthreads=THREADS, flags=tthip.TT_SHADOW_VISIBILITY_CHECK if visibility_check else 0)
+    assert st == 0
+    return after, vis, col, nee, cnt["status"]
+
+
+@pytest.mark.parametrize("visibility_check", [False, True], ids=["default", "vischeck"])
+@pytest.mark.parametrize("bounce", [0, 1])
+@pytest.mark.parametrize("name,ray_set", SHADOW_CASES)
+def test_any_hit_matrix(name, ray_set, bounce, visibility_check):
+    before, W, H = shadow_rays(name, ray_set)
+    after, vis, col, nee, status = oracle_any_hit(C.scene(name, "shadow"), before, W, H, bounce, visibility_check)
+    ref = C.reference_any_hit(C.geometry(name, "shadow"), before, visibility_check)
+    C.compare_any_hit(ref, before, after, vis, col, nee, bounce, visibility_check, status).check()
+
+
+# ------------------------------------------------------------------ the comparison must be able to fail
+def test_comparison_fails_for_a_reference_without_invisible():
+    rays = closest_rays("soup", "random")
+    hits = oracle_closest(C.scene("soup"), rays, 0, 0)
+    wrong = C.reference_closest(C.geometry("soup"), rays, len(hits), 0, 0, honour_invisible=False)
+    rep = C.compare_closest(wrong, hits)
+    assert rep.mismatches > 0 and rep.failures, rep.text
+
+
+def test_comparison_fails_for_a_reference_without_shadow_tags():
+    before, W, H = shadow_rays("soup", "random")
+    after, vis, col, nee, status = oracle_any_hit(C.scene("soup", "shadow"), before, W, H, 0, False)
+    wrong = C.reference_any_hit(C.geometry("soup", "shadow"), before, honour_tags=False)
+    rep = C.compare_any_hit(wrong, before, after, vis, col, nee, 0, False, status)
+    assert rep.mismatches > 0 and rep.failures, rep.text
+
+
+def test_comparison_fails_for_a_blas_root_that_lost_a_child():
+    """The oracle walks a scene whose BLAS root has the meta byte of one live child zeroed (the child is never
+    entered); the reference sees the true triangles."""
+    sc = C.scene("soup")
+    root = int(sc.meshdata["mesh_data_bvh_offsets"][0]) & 0x7FFFFFFF
+    nodes = sc.nodes.copy()
+    meta = nodes[root:root + 1]["meta"].copy().view(np.uint8).reshape(8)
+    live = np.nonzero(meta)[0]
+    assert len(live) > 1
+    meta[live[0]] = 0
+    nodes["meta"][root] = meta.view(np.uint32)
+    rays = closest_rays("soup", "random")
+    hits = oracle_closest(dataclasses.replace(sc, nodes=nodes), rays, 0, 0)
+    rep = C.compare_closest(C.reference_closest(C.geometry("soup"), rays, len(hits), 0, 0), hits)
+    assert rep.mismatches > 0 and rep.failures, rep.text
+
+
+# ------------------------------------------------------------------ after the refits
+def test_closest_after_a_blas_refit_of_deformed_vertices():
+    """The oracle's BLAS refit (then its TLAS refit, as a caller runs them) of the soup under a smooth
+    displacement; the reference sees triangles rebuilt in float64 from the deformed vertex array."""
+    sc, pos, idx, leaf = C.refit_soup()
+    V = C.deformed_vertices(pos)
+    st, nodes, tris = O.blas_refit(sc, 0, C.vertex_buffer(V), idx, leaf)
+    assert st == 0
+    g = C.deformed_geometry(sc, 0, V, idx, leaf)
+    sc2 = dataclasses.replace(sc, nodes=nodes, tris=tris)
+    st, nodes2 = O.tlas_refit(sc2, C.world_boxes(g))
+    assert st == 0
+    o, d = C.random_rays(g, 31, N_RAYS)
+    rays = C.ray_buffer(o, d)
+    hits = oracle_closest(dataclasses.replace(sc2, nodes=nodes2), rays, 0, 0)
+    C.compare_closest(C.reference_closest(g, rays, N_RAYS, 0, 0), hits).check()
+
+
+def test_closest_after_a_tlas_refit_of_moved_instances():
+    """Six of the twelve instances moved: new mesh records, world boxes from the moved triangles, the TLAS
+    refit with its topology kept; the reference uses the new W2L."""
+    a, meshdata, g, boxes = C.moved_instances()
+    moved = dataclasses.replace(a, meshdata=meshdata)
+    st, nodes = O.tlas_refit(moved, boxes)
+    assert st == 0
+    o, d = C.random_rays(g, 32, N_RAYS)
+    rays = C.ray_buffer(o, d)
+    hits = oracle_closest(dataclasses.replace(moved, nodes=nodes), rays, 0, 0)
+    C.compare_closest(C.reference_closest(g, rays, N_RAYS, 0, 0), hits).check()
