@@ -13,6 +13,10 @@ C4 (argument c4). Counters (csrc/tt_trace.hip, tt_wide.h; wave executions unless
  24/25/26 drain triangle passes (G = 2/4/8)   27 rays in drain triangle passes
  28 chunk-setup node steps (TT_LEAF_ROOT_STEP: the BLAS root's step of a whole chunk)
  29 lanes in chunk-setup node steps (rays that hit the TLAS root's box)
+ 30 idle lanes (lanes without a ray after the refill block, summed over the loop iterations)
+ 31 lanes finishing in advance blocks   32 advance blocks in which at least one lane finishes
+ 33 lanes restarted in the advance (TT_LEAF_RESTART: the next prepared ray taken from the pool at once)
+ 34 full-width writes of parked results (TT_LEAF_RESTART)   35 records they write
 
 Weighted by each block's static VALU count (tools/isa_blocks.py on the product kernel's ISA; the
 table is --static JSON), this gives VALU per ray by block. Output: JSON on stdout."""
@@ -27,7 +31,9 @@ NAMES = ["iterations", "record_batches", "refills", "dequeues", "ray_setups", "n
          "tlas_leaf", "tri_passes", "advance", "pops", "blas_exits", "drain_entries", "drain_iters_g2",
          "drain_iters_g4", "drain_iters_g8", "lanes_node", "lanes_tri", "lanes_refilled", "drain_node_g2",
          "drain_node_g4", "drain_node_g8", "drain_node_rays", "drain_tri_g2", "drain_tri_g4", "drain_tri_g8",
-         "drain_tri_rays", "setup_node_steps", "lanes_setup_node"]
+         "drain_tri_rays", "setup_node_steps", "lanes_setup_node", "idle_lanes", "lanes_finishing",
+         "advance_finishing", "lanes_restarted", "flushes", "records_flushed"]
+N_COUNTERS = 64  # the kernel adds TT_DB_N (40) counters; the rest stays zero
 
 
 def main():
@@ -41,7 +47,7 @@ def main():
     scene_fn, view = {"c2": (T.c2_sponza, T.C2_VIEW), "c4": (T.c4_bistro, T.C4_VIEW)}[cfg]
     sc = scene_fn()
     dev = torch.device("cuda:0")
-    cnt = torch.zeros(32, dtype=torch.int64, device=dev)
+    cnt = torch.zeros(N_COUNTERS, dtype=torch.int64, device=dev)
     os.environ["TT_DIAG_PTR"] = str(cnt.data_ptr())
     eng = tthip.Engine(0, stream=torch.cuda.current_stream(dev).cuda_stream)
     eng.upload(sc)
@@ -73,6 +79,16 @@ def main():
         rec["lanes_per_tri_pass"] = round(c[18] / max(c[9], 1), 2)
         rec["lanes_per_refill"] = round(c[19] / max(c[4], 1), 2)
         rec["lanes_per_setup_node_step"] = round(c[29] / max(c[28], 1), 2)
+        # lane utilisation: idle lanes per loop iteration, and what they cost at 305 VALU per iteration whatever
+        # the exec mask (idle lane-iterations per ray / 64 x 305)
+        rec["idle_lanes_per_iteration"] = round(c[30] / max(c[0], 1), 2)
+        rec["idle_valu_per_ray"] = round(c[30] / n / 64.0 * 305.0, 2)
+        rec["lanes_finishing_per_advance"] = round(c[31] / max(c[10], 1), 3)
+        rec["advance_share_with_a_finish"] = round(c[32] / max(c[10], 1), 4)
+        rec["restarts_per_advance"] = round(c[33] / max(c[10], 1), 3)
+        rec["restarted_share_of_finishing"] = round(c[33] / max(c[31], 1), 4)
+        rec["flushes_per_ray"] = round(c[34] / n, 5)
+        rec["records_per_flush"] = round(c[35] / max(c[34], 1), 2)
         # every node step of a ray: the loop's lanes, the drain's rays and the chunk setup's lanes
         rec["node_steps_per_ray"] = round((c[17] + c[23] + (c[29] if c[28] else 0)) / n, 4)
         rec["drain_node_share"] = round(c[23] / max(c[17] + c[23], 1), 4)

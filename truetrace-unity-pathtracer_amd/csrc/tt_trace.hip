@@ -197,6 +197,15 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     // the step: Reps 2, the hit inner children in cg and the hit leaf triangles in tg, or an empty group.
     constexpr bool POOL = LEAF != 0 && TT_LEAF_POOL != 0;
     constexpr bool ROOTSTEP = POOL && TT_LEAF_ROOT_STEP != 0;
+    // RESTART (TT_LEAF_RESTART): a lane whose ray finishes while the pool holds prepared rays takes the next one in
+    // the same advance block. The finished ray's result is parked in the slot just consumed -- word 0: (tri_id, t, u,
+    // v), word 1: (work index, PixelIndex) -- and bit `slot` of the wave-uniform mask `parked` is set; lane s writes
+    // the record of slot s, through write_record, before a chunk setup overwrites the pool, before the cooperative
+    // drain and at the loop's exit. A lane's ray_index holds the ray's WORK index (ray_of() maps it where a record
+    // is written), and the INFO 2 record's world ray is read back from RayData words 0-1 by the full-width write
+    // (the form LEAF == 1), so no lane keeps it.
+    constexpr bool RESTART = ROOTSTEP && TT_LEAF_RESTART != 0;
+    static_assert(!RESTART || LEAF == 1, "the restart parks no world ray: the record write reads it back");
     constexpr int tt_lds_depth = lds_depth_of<LEAF>();  // the LDS part of the stack (TT_PUSH / TT_POP)
     static_assert(!POOL || TT_CHUNK_BIG == TT_WAVE, "the prepared-ray pool holds one chunk, one slot per lane");
     __shared__ uint2 s_stack[tt_lds_depth][TT_BLOCK];
@@ -280,6 +289,14 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
         return A.ray_offset + local;
     };
     (void)ray_of;
+    // RESTART: bit s = slot s of the pool holds a parked result (wave-uniform)
+    uint64_t parked = 0ull;
+    (void)parked;
+    // the ray index of a lane's ray_index word (RESTART keeps the work index there)
+    auto ray_index_of = [&](uint32_t v) -> uint32_t {
+        if constexpr (RESTART) return ray_of(v);
+        return v;
+    };
 
 #if TT_ROOT_LEAF
     const bool rl_ok = A.root.ok != 0u;  // a kernel argument: wave-uniform
@@ -311,11 +328,62 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     };
     // :229-241: the finished ray's hit record and _PrimaryTriangleInfo
     auto finish_ray = [&]() {
-        const bool hit = write_record<INFO, LEAF>(A, ray_index, pix, col_w, best, world_ray(), mesh_id, TriOffset);
+        const bool hit = write_record<INFO, LEAF>(A, ray_index_of(ray_index), pix, col_w, best, world_ray(), mesh_id,
+                                                  TriOffset);
         if (STATS) c_hits += hit ? 1u : 0u;
         (void)hit;
         if (ORD) record_chunk_cost(A, swizzle, ray_index, Reps);
     };
+    // POOL: a lane's start on work index widx from the pool record of its slot
+    auto start_from = [&](const uint32_t widx, const uint4 p0, const uint4 p1, const uint4 p2) {
+        TT_DL(19, true);
+        ray_index = RESTART ? widx : ray_of(widx);
+        ray.ox = __uint_as_float(p0.x);
+        ray.oy = __uint_as_float(p0.y);
+        ray.oz = __uint_as_float(p0.z);
+        ray.dx = __uint_as_float(p0.w);
+        ray.dy = __uint_as_float(p1.x);
+        ray.dz = __uint_as_float(p1.y);
+        ray.ix = __uint_as_float(p1.z);
+        ray.iy = __uint_as_float(p1.w);
+        ray.iz = __uint_as_float(p2.x);
+        pix = p2.y;
+        if (ROOTSTEP) {
+            col_w = -1.0f;  // (the setup has made write_record's test of Data.w: see there)
+            oct = p2.z & 0x7fffffffu;
+            // node_group / tri_group of the setup's step. Without a hit inner child the node group is
+            // empty -- in the loop the advance follows such a step at once, here the node phase comes
+            // first -- and so is a ray's that missed the root's box (mask 0): the advance finishes it
+            const uint32_t inner = p2.w & 0xff000000u;
+            cg = make_uint2(root_cg_x, inner ? (inner | root_imask) : 0u);
+            tg = make_uint2(root_tg_x, p2.w & 0x00ffffffu);
+            Reps = (p2.z & 0x80000000u) ? 2 : 1;
+        } else {
+            col_w = __uint_as_float(p2.z);
+            oct = p2.w & 0x7fffffffu;
+            // a ray that missed the root's box starts with the empty group: the advance finishes it
+            cg = make_uint2((p2.w & 0x80000000u) ? (uint32_t)L.off.w : 0u, p2.w & 0x80000000u);
+        }
+        if (LEAF == 2) {  // the world ray of the INFO = 2 record: the chunk's setup has just read the lines
+            const uint4* rp = reinterpret_cast<const uint4*>(A.rays + ray_index);
+            const uint4 r0 = rp[0], r1 = rp[1];
+            wray.ox = __uint_as_float(r0.x);
+            wray.oy = __uint_as_float(r0.y);
+            wray.oz = __uint_as_float(r0.z);
+            wray.dx = __uint_as_float(r1.x);
+            wray.dy = __uint_as_float(r1.y);
+            wray.dz = __uint_as_float(r1.z);
+        }
+        best.t = A.far_plane;
+        best.u = 0.0f;
+        best.v = 0.0f;
+        best.mesh_id = 0;
+        best.tri_id = -1;
+        if (!ROOTSTEP) tg = make_uint2(0u, 0u);
+        stack_size = 0;
+        if (!ROOTSTEP) Reps = 1;
+    };
+    (void)start_from;
     // (the leaf form's ray start is cheaper, so its refill threshold is a knob of its own)
     constexpr uint32_t REFILL_MIN = LEAF ? TT_LEAF_REFILL_MIN : TT_REFILL_MIN;
     while (true) {
@@ -332,12 +400,37 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
 #endif
         // the queue is dry and the live rays fit in 2-lane groups: cooperative drain (tt_wide.h)
         const bool to_wide = TT_WIDE && pool_dry && n_idle < TT_WAVE && TT_WAVE - n_idle <= TT_WIDE_ENTER;
+        // RESTART: lanes only idle for want of a prepared ray, so the pool-empty case has a threshold of its own
+        // (the few lanes a Reps bound or a stack overflow idles wait as before while the pool holds rays)
+        const uint32_t refill_min = RESTART && pool_next >= pool_end ? (uint32_t)TT_LEAF_RESTART_MIN : REFILL_MIN;
         // finished rays write their records in batches, right before their lanes are refilled
-        if ((n_idle == TT_WAVE && pool_dry) || (n_idle >= REFILL_MIN && !pool_dry) || to_wide) {
+        if ((n_idle == TT_WAVE && pool_dry) || (n_idle >= refill_min && !pool_dry) || to_wide) {
             if (pending) {
                 TT_DB(1);
                 finish_ray();
                 pending = false;
+            }
+            if constexpr (RESTART) {
+                // the parked results, at full width: lane s writes the record of slot s. Before the refill below
+                // overwrites the pool, before the drain regroups the lanes and before the wave ends.
+                if (parked != 0ull) {
+                    TT_DB(34);
+                    if ((parked >> lane) & 1ull) {
+                        TT_DL(35, true);
+                        const uint4 k0 = s_pool[0][tid];
+                        const uint2 k1 = reinterpret_cast<const uint2*>(&s_pool[1][tid])[0];
+                        Best kb;
+                        kb.tri_id = (int32_t)k0.x;
+                        kb.t = __uint_as_float(k0.y);
+                        kb.u = __uint_as_float(k0.z);
+                        kb.v = __uint_as_float(k0.w);
+                        kb.mesh_id = 0;
+                        write_record<INFO, LEAF>(A, ray_of(k1.x), k1.y, -1.0f, kb, LaneRay{}, mesh_id, TriOffset);
+                    }
+                    parked = 0ull;
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                }
             }
         }
         if (n_idle == TT_WAVE && pool_dry) break;
@@ -345,7 +438,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
         if (to_wide) {
             TT_DB(13);
             WideState st{{ray, world_ray(), cg, tg, oct, stack_size, tlas_ss, NodeOffset, TriOffset, MatOffset, Reps,
-                          ray_index, tid, gtid, (int32_t)tg.y >= 0},
+                          ray_index_of(ray_index), tid, gtid, (int32_t)tg.y >= 0},
                          best, mesh_id, pix, col_w};
             regroup<2, LEAF>(st, __ballot((int32_t)tg.y >= 0), lane);
             auto finish_wide = [&](const WideState& w) {
@@ -363,7 +456,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
             break;
         }
 #endif
-        if (n_idle >= REFILL_MIN && !pool_dry) {
+        if (n_idle >= refill_min && !pool_dry) {
             TT_DB(2);
 #if TT_LONG_PRIO
             // a wave carrying a long ray (>= TT_LONG_PRIO node steps so far) issues ahead of the others until
@@ -393,55 +486,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                 const bool take = (int32_t)tg.y < 0 && widx != 0xffffffffu;
                 // slots left from the previous chunk are read before the new chunk overwrites the pool
                 const bool take_left = take && lane_prefix(idle) < min(avail, n_idle);
-                // a lane's start from the record of its slot
-                auto start_ray = [&](const uint4 p0, const uint4 p1, const uint4 p2) {
-                    TT_DL(19, true);
-                    ray_index = ray_of(widx);
-                    ray.ox = __uint_as_float(p0.x);
-                    ray.oy = __uint_as_float(p0.y);
-                    ray.oz = __uint_as_float(p0.z);
-                    ray.dx = __uint_as_float(p0.w);
-                    ray.dy = __uint_as_float(p1.x);
-                    ray.dz = __uint_as_float(p1.y);
-                    ray.ix = __uint_as_float(p1.z);
-                    ray.iy = __uint_as_float(p1.w);
-                    ray.iz = __uint_as_float(p2.x);
-                    pix = p2.y;
-                    if (ROOTSTEP) {
-                        col_w = -1.0f;  // (the setup has made write_record's test of Data.w: see there)
-                        oct = p2.z & 0x7fffffffu;
-                        // node_group / tri_group of the setup's step. Without a hit inner child the node group is
-                        // empty -- in the loop the advance follows such a step at once, here the node phase comes
-                        // first -- and so is a ray's that missed the root's box (mask 0): the advance finishes it
-                        const uint32_t inner = p2.w & 0xff000000u;
-                        cg = make_uint2(root_cg_x, inner ? (inner | root_imask) : 0u);
-                        tg = make_uint2(root_tg_x, p2.w & 0x00ffffffu);
-                        Reps = (p2.z & 0x80000000u) ? 2 : 1;
-                    } else {
-                        col_w = __uint_as_float(p2.z);
-                        oct = p2.w & 0x7fffffffu;
-                        // a ray that missed the root's box starts with the empty group: the advance finishes it
-                        cg = make_uint2((p2.w & 0x80000000u) ? (uint32_t)L.off.w : 0u, p2.w & 0x80000000u);
-                    }
-                    if (LEAF == 2) {  // the world ray of the INFO = 2 record: the chunk's setup has just read the lines
-                        const uint4* rp = reinterpret_cast<const uint4*>(A.rays + ray_index);
-                        const uint4 r0 = rp[0], r1 = rp[1];
-                        wray.ox = __uint_as_float(r0.x);
-                        wray.oy = __uint_as_float(r0.y);
-                        wray.oz = __uint_as_float(r0.z);
-                        wray.dx = __uint_as_float(r1.x);
-                        wray.dy = __uint_as_float(r1.y);
-                        wray.dz = __uint_as_float(r1.z);
-                    }
-                    best.t = A.far_plane;
-                    best.u = 0.0f;
-                    best.v = 0.0f;
-                    best.mesh_id = 0;
-                    best.tri_id = -1;
-                    if (!ROOTSTEP) tg = make_uint2(0u, 0u);
-                    stack_size = 0;
-                    if (!ROOTSTEP) Reps = 1;
-                };
+                auto start_ray = [&](const uint4 p0, const uint4 p1, const uint4 p2) { start_from(widx, p0, p1, p2); };
                 uint4 p0 = make_uint4(0u, 0u, 0u, 0u), p1 = p0, p2 = p0;
                 if (take_left) {
                     const uint32_t slot = pcol + (widx & 63u);
@@ -590,6 +635,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
             }
         }
 
+        TT_DL(30, (int32_t)tg.y < 0);  // lanes that sit this iteration out
         // ------------------------------------------------------------- node phase
         // valu_mix:node:begin
         if (STATS) {  // SIMD-efficiency diagnostics (wave-uniform; lane 0 accumulates)
@@ -608,7 +654,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
             if (Reps >= TT_MAX_REPS) {
                 tg.y = TT_IDLE;  // loop bound hit: the reference writes nothing
                 if (STATS) c_reps++;
-                keep_record(A, ray_index);
+                keep_record(A, ray_index_of(ray_index));
                 if (ORD) record_chunk_cost(A, swizzle, ray_index, Reps);
             } else if (cg.y & 0xff000000u) {  // IntersectionKernels.compute:157-187
                 const uint32_t child = take_child(cg, oct);
@@ -636,7 +682,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                     tg.y = TT_IDLE;
                     if (STATS) c_ovf++;
                     TT_REPORT_OVERFLOW(A);
-                    keep_record(A, ray_index);
+                    keep_record(A, ray_index_of(ray_index));
                 }
             } else {  // :188-191
                 tg = cg;
@@ -672,8 +718,56 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
         // ----------------------------------------- advance: pop / finish (:228-251)
         // One place for every lane whose group is used up, whether it came from a node step or
         // from its last triangle this pass (equivalent order: the reference pops right after).
-        if (tg.y == 0u && (cg.y & 0xff000000u) == 0u) {
+        if constexpr (RESTART) {
+            // The same advance with the restart. Which lanes finish is balloted outside the divergent block, so that
+            // the pool state stays wave-uniform (SGPRs); the path without a finishing lane is one pop.
+            const bool used_up = tg.y == 0u && (cg.y & 0xff000000u) == 0u;
+            const bool finishing = used_up && stack_size == 0;
+            if (used_up) {
+                TT_DB(10);
+                TT_DL(31, finishing);
+                if (stack_size != 0) {
+                    TT_DB(11);
+                    TT_POP(cg);
+                }
+            }
+            const uint64_t fin = __ballot(finishing);
+            if (fin != 0ull) {  // wave-uniform
+                TT_DB(32);
+                const uint32_t n_fin = (uint32_t)__builtin_popcount((uint32_t)fin) + (uint32_t)__builtin_popcount((uint32_t)(fin >> 32));
+                const uint32_t n_take = min(n_fin, pool_end - pool_next);  // (pool_next <= pool_end always)
+                if (finishing) {
+                    const uint32_t rank = lane_prefix(fin);
+                    if (rank < n_take) {
+                        TT_DL(33, true);
+                        // the next prepared ray's record out of its slot, the finished ray's result into it
+                        const uint32_t widx = pool_next + rank;
+                        const uint32_t slot = (tid - lane) + (widx & 63u);
+                        const uint4 p0 = s_pool[0][slot], p1 = s_pool[1][slot], p2 = s_pool[2][slot];
+#ifdef TT_TEST_PARK_SWAP  // (tests only: a wrong parked word must show in the records)
+                        s_pool[0][slot] = make_uint4((uint32_t)best.tri_id, __float_as_uint(best.t), __float_as_uint(best.v),
+                                                     __float_as_uint(best.u));
+#else
+                        s_pool[0][slot] = make_uint4((uint32_t)best.tri_id, __float_as_uint(best.t), __float_as_uint(best.u),
+                                                     __float_as_uint(best.v));
+#endif
+                        reinterpret_cast<uint2*>(&s_pool[1][slot])[0] = make_uint2(ray_index, pix);
+                        start_from(widx, p0, p1, p2);
+                    } else {
+                        pending = true;  // no prepared ray left: written at the next refill (or when the wave drains)
+                        tg.y = TT_IDLE;
+                    }
+                }
+                if (n_take != 0u) {  // slots [pool_next, pool_next + n_take) of one chunk-aligned chunk: no wrap
+                    const uint64_t m = n_take >= 64u ? ~0ull : ((1ull << n_take) - 1ull);
+                    parked |= m << (pool_next & 63u);
+                    pool_next += n_take;
+                }
+            }
+        } else if (tg.y == 0u && (cg.y & 0xff000000u) == 0u) {
             TT_DB(10);
+            TT_DL(31, stack_size == 0);
+            if (stack_size == 0) TT_DB(32);
             if (stack_size != 0) {
                 TT_DB(11);
                 if (!LEAF && stack_size == tlas_ss) {
@@ -746,7 +840,10 @@ __global__ TT_BOUNDS void tt_trace_kernel_ord_mat(TraceArgs A) {
 #ifndef TT_LEAF_WRAY_RESIDENT
 #define TT_LEAF_WRAY_RESIDENT 1
 #endif
-#define TT_LEAF_FORM(INFO) ((INFO) == 2 && TT_LEAF_WRAY_RESIDENT ? 2 : 1)
+// (with TT_LEAF_RESTART no lane keeps it: finished rays' records are written at full width from the pool, where the
+// re-read costs one pass per chunk)
+#define TT_LEAF_FORM(INFO) \
+    ((INFO) == 2 && TT_LEAF_WRAY_RESIDENT && !(TT_LEAF_POOL && TT_LEAF_ROOT_STEP && TT_LEAF_RESTART) ? 2 : 1)
 // (IND, INFO: the profile summaries bench.py reads key a kernel by its name's last template argument, INFO)
 template <bool IND, int INFO>
 __global__ TT_LEAF_BOUNDS void tt_trace_leaf_kernel(TraceArgs A) {

@@ -62,6 +62,18 @@
 #ifndef TT_LEAF_ROOT_STEP
 #define TT_LEAF_ROOT_STEP 1
 #endif
+// With the pool and the root step, a lane whose ray finishes takes its next prepared ray from the pool in the same
+// advance block instead of idling until TT_LEAF_REFILL_MIN lanes have finished: the finished ray's result is parked
+// in the pool slot just consumed and its record is written later, at full width, before the pool is overwritten
+// (TT_LEAF_RESTART 1; 0: finished lanes wait for the refill, A/B). The refill block then only runs when the pool is
+// empty, once TT_LEAF_RESTART_MIN lanes are idle (the chunk setup is full-width work however few lanes wait for it,
+// but 1 / 4 / 8 / 12 measured no better than 16 and 20 and more worse: profiles/r15/restart/ab.json).
+#ifndef TT_LEAF_RESTART
+#define TT_LEAF_RESTART 1
+#endif
+#ifndef TT_LEAF_RESTART_MIN
+#define TT_LEAF_RESTART_MIN 16
+#endif
 #ifndef TT_WAVES_PER_EU
 #define TT_WAVES_PER_EU 0 // __launch_bounds__ min waves per SIMD (0: compiler default)
 #endif
@@ -75,7 +87,7 @@
 // the closest-hit loop in LDS, flushed to TraceArgs::diag_times at the end of the launch. TT_DB(k): one
 // wave execution of block k (counted by the first active lane); TT_DL(k, pred): lanes with pred.
 #ifdef TT_DIAG_BLOCKS
-#define TT_DB_N 32
+#define TT_DB_N 40
 __shared__ unsigned long long tt_db[TT_DB_N];
 #define TT_DB(k)                                                                               \
     do {                                                                                       \
