@@ -23,6 +23,7 @@ namespace TrueTrace.Hip
         IgnoreGlass = 1u << 5,       // IgnoreGlassMain  (IntersectionKernels.compute:42-44)
         IgnoreBackfacing = 1u << 6,  // IgnoreBackfacing (IntersectionKernels.compute:45-47)
         AdaptiveOrder = 1u << 7,     // dequeue the previous launch's costliest 8x8 tiles first (same results)
+        TerrainBounce = 1u << 8,     // tt_enqueue_diffuse_bounce(_indirect): terrain hits bounce off the terrain
         RadianceCache = 1u << 7,     // tt_trace_shadow_ex: the RadianceCache define (GlobalDefines.cginc:15)
         VisibilityCheck = 1u << 8    // tt_trace_shadow_ex: VisabilityCheckCompute (CommonData.cginc:710-819)
     }
@@ -213,6 +214,8 @@ namespace TrueTrace.Hip
         // device memory as the flags say (TT_TRACE_DEVICE_PTRS); the _indirect forms read their count on the device.
         [DllImport(Lib)] public static extern TTStatus tt_trace_heightmap(IntPtr ctx, ref TTTraceParams p, IntPtr globalRays,
             IntPtr primaryInfo, out TTStats stats);
+        [DllImport(Lib)] public static extern TTStatus tt_trace_heightmap_hits(IntPtr ctx, ref TTTraceParams p,
+            IntPtr globalRays, IntPtr primaryInfo, IntPtr hitsOut);
         [DllImport(Lib)] public static extern TTStatus tt_trace_heightmap_indirect(IntPtr ctx, ref TTTraceParams p,
             IntPtr nRaysDev, IntPtr globalRays, IntPtr primaryInfo);
         [DllImport(Lib)] public static extern TTStatus tt_trace_shadow_heightmap(IntPtr ctx, ref TTShadowParams p,
@@ -268,6 +271,8 @@ namespace TrueTrace.Hip
             uint width, uint height);
         [DllImport(Lib)] public static extern unsafe TTStatus tt_group_scene_upload_texture_atlas(IntPtr group,
             ushort* rgbaHalf, uint width, uint height);
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_group_scene_upload_terrains(IntPtr group, TtTerrain* terrains,
+            uint n, ushort* heightmapHalf, uint width, uint height);
         [DllImport(Lib)] public static extern unsafe TTStatus tt_group_scene_update_meshdata(IntPtr group, uint first,
             uint count, void* meshData);
         [DllImport(Lib)] public static extern unsafe TTStatus tt_group_scene_update_nodes(IntPtr group, uint first,
@@ -349,10 +354,11 @@ namespace TrueTrace.Hip
         /// production, RayTracingShader.compute:498-506): survivors compacted into the other ping-pong half;
         /// returns their count (synchronises).
         public uint EnqueueDiffuseBounce(IntPtr globalRays, uint nRays, int curBounce, float farPlane, int width, int height,
-                                         int framesAccumulated, int maxBounce)
+                                         int framesAccumulated, int maxBounce, bool terrainBounce = false)
         {
             var p = new TTTraceParams { nRays = nRays, bounce = curBounce, farPlane = farPlane, screenWidth = (uint)width,
-                                        screenHeight = (uint)height, flags = TTTraceFlags.DevicePtrs };
+                                        screenHeight = (uint)height,
+                                        flags = TTTraceFlags.DevicePtrs | (terrainBounce ? TTTraceFlags.TerrainBounce : 0) };
             Check(Native.tt_enqueue_diffuse_bounce(m_ctx, ref p, globalRays, framesAccumulated, maxBounce, out uint n));
             return n;
         }
@@ -362,10 +368,11 @@ namespace TrueTrace.Hip
         /// Generate -> TraceDevice -> EnqueueDiffuseBounceIndirect -> TraceDeviceIndirect is one device chain.
         public void EnqueueDiffuseBounceIndirect(IntPtr globalRays, IntPtr nRaysDevice, uint capacity, int curBounce,
                                                  float farPlane, int width, int height, int framesAccumulated,
-                                                 int maxBounce, IntPtr nNextDevice)
+                                                 int maxBounce, IntPtr nNextDevice, bool terrainBounce = false)
         {
             var p = new TTTraceParams { nRays = capacity, bounce = curBounce, farPlane = farPlane, screenWidth = (uint)width,
-                                        screenHeight = (uint)height, flags = TTTraceFlags.DevicePtrs };
+                                        screenHeight = (uint)height,
+                                        flags = TTTraceFlags.DevicePtrs | (terrainBounce ? TTTraceFlags.TerrainBounce : 0) };
             Check(Native.tt_enqueue_diffuse_bounce_indirect(m_ctx, ref p, nRaysDevice, globalRays, framesAccumulated,
                                                             maxBounce, nNextDevice));
         }
@@ -632,6 +639,18 @@ namespace TrueTrace.Hip
             return s;
         }
 
+        /// TraceHeightmapDevice that also writes every record it rewrites into `hitsOut`, the contiguous hit stream
+        /// TraceDeviceHits filled for the same rays (tt_trace_heightmap_hits): afterwards it holds every ray's record.
+        public void TraceHeightmapDeviceHits(IntPtr globalRays, uint nRays, int curBounce, float farPlane, int width,
+                                             int height, IntPtr hitsOut, IntPtr primaryInfo = default,
+                                             TTTraceFlags flags = 0, bool async = false)
+        {
+            var p = new TTTraceParams { nRays = nRays, bounce = curBounce, farPlane = farPlane, screenWidth = (uint)width,
+                                        screenHeight = (uint)height,
+                                        flags = flags | TTTraceFlags.DevicePtrs | (async ? TTTraceFlags.Async : 0) };
+            Check(Native.tt_trace_heightmap_hits(m_ctx, ref p, globalRays, primaryInfo, hitsOut));
+        }
+
         /// The same with BufferSizes[CurBounce].heighmap_rays on the GPU (no host round trip).
         public void TraceHeightmapIndirect(IntPtr globalRays, IntPtr nRaysDev, uint capacity, int curBounce, float farPlane,
                                            int width, int height, IntPtr primaryInfo = default, TTTraceFlags flags = 0)
@@ -881,6 +900,13 @@ namespace TrueTrace.Hip
         public unsafe void SetTextureAtlas(ushort[] rgbaHalf, int width, int height)
         {
             fixed (ushort* t = rgbaHalf) Check(Native.tt_group_scene_upload_texture_atlas(m_g, t, (uint)width, (uint)height));
+        }
+        /// The Terrains / Heightmap bindings on every device: frames then march the terrains after each trace and
+        /// bounce off terrain hits. An empty array clears the set.
+        public unsafe void SetTerrains(TtTerrain[] terrains, ushort[] heightmapHalf, int width, int height)
+        {
+            fixed (TtTerrain* t = terrains) fixed (ushort* h = heightmapHalf)
+                Check(Native.tt_group_scene_upload_terrains(m_g, t, (uint)(terrains?.Length ?? 0), h, (uint)width, (uint)height));
         }
 
         /// One frame: Generate + primary trace per device for its tiles, the gather of the primary hit records to

@@ -436,8 +436,8 @@ TT_STATIC_ASSERT(sizeof(tt_terrain) == 60, "TerrainData is 60 bytes");
  * the atlases: contexts sharing the scene (tt_ctx_share_scene / _blas) see it, the call is refused while
  * borrowers exist, and a later tt_scene_upload keeps it. Every field must be finite and every HeightMap
  * rectangle must lie in [0, 1] (TT_ERR_INVALID_ARG, reason in tt_last_error). Filtering is pinned as the
- * alpha atlas's linear filter, applied to exactly decoded half texels. tt_group_* does not learn terrains:
- * a host with terrains traces them on the member contexts (tt_group_member_ctx). */
+ * alpha atlas's linear filter, applied to exactly decoded half texels. A group's members take their set
+ * through tt_group_scene_upload_terrains (a member's slot contexts borrow its scene context's scene). */
 tt_status tt_scene_upload_terrains(tt_ctx* ctx, const tt_terrain* terrains, uint32_t n,
                                    const uint16_t* heightmap_half, uint32_t width, uint32_t height);
 /* The check tt_scene_upload_terrains runs (host only, no device needed). why (nullable) receives the first
@@ -595,7 +595,11 @@ enum {
      * changes, what is written does not: results are identical to an unflagged launch. The
      * reference pops rays in InterlockedAdd order (IntersectionKernels.compute:79-81), so no order
      * is part of its contract. */
-    TT_TRACE_ADAPTIVE_ORDER = 1u << 7
+    TT_TRACE_ADAPTIVE_ORDER = 1u << 7,
+    /* tt_enqueue_diffuse_bounce(_indirect) only (every other call ignores it): on a context with terrains a
+     * terrain hit bounces off the terrain instead of ending its path. Bit 8 of tt_shadow_params.flags is
+     * TT_SHADOW_VISIBILITY_CHECK; the two never meet in one params struct. */
+    TT_ENQUEUE_TERRAIN_BOUNCE = 1u << 8
 };
 
 typedef struct tt_trace_params {
@@ -820,6 +824,14 @@ tt_status tt_trace_shadow_ex_indirect(tt_ctx* ctx, const tt_shadow_params* p, co
  * of the march kernels instead, which measured slower and gives identical results. */
 tt_status tt_trace_heightmap(tt_ctx* ctx, const tt_trace_params* p, tt_ray_data* global_rays,
                              uint32_t* primary_info, tt_stats* stats);
+/* tt_trace_heightmap that also writes every record it rewrites to the contiguous hit stream: whenever the march
+ * rewrites ray i of the launch, the same 16 bytes go to hits_out[4 i .. 4 i + 3]; records of rays it does not
+ * rewrite are not touched. hits_out is the buffer tt_trace_closest_hits just filled for the same rays, so after
+ * both calls it equals RayData.hits of every ray (what a tile-sharded frame gathers). Requires
+ * TT_TRACE_DEVICE_PTRS and 16-byte-aligned device memory of n_rays records; TT_TRACE_STATS is
+ * TT_ERR_INVALID_ARG. Everything else is tt_trace_heightmap's. */
+tt_status tt_trace_heightmap_hits(tt_ctx* ctx, const tt_trace_params* p, tt_ray_data* global_rays,
+                                  uint32_t* primary_info, uint32_t* hits_out);
 /* The same with a device-resident ray count: the contract of tt_trace_closest_indirect. */
 tt_status tt_trace_heightmap_indirect(tt_ctx* ctx, const tt_trace_params* p, const uint32_t* n_rays_dev,
                                       tt_ray_data* global_rays, uint32_t* primary_info);
@@ -888,9 +900,15 @@ tt_status tt_generate_primary(tt_ctx* ctx, const tt_camera* cam, tt_ray_data* gl
  * source order (a stable single-pass scan: 4096-ray tiles, block ballot / LDS prefix, decoupled
  * look-back over the preceding tiles' counts; the reference's InterlockedAdd order,
  * RayTracingShader.compute:500, is whatever its atomics serialise to); *n_next receives their
- * count. On a context with terrains a hit with mesh_id == TT_TERRAIN_MESH_ID terminates its path (bouncing
- * off terrain needs the terrain normal inside kernel_shade's subset: not built yet); without a terrain set
- * nothing changes. */
+ * count. On a context with terrains a hit with mesh_id == TT_TERRAIN_MESH_ID terminates its path, unless
+ * p->flags has TT_ENQUEUE_TERRAIN_BOUNCE: then a terrain record with triangle_id < the terrain count survives
+ * under the triangle rule (t < far_plane, pdf > 0 from the same random(1, pixel) draw) and its new ray is the
+ * diffuse subset's terrain branch (RayTracingShader.compute:109-111): Geomnorm = USGNorm =
+ * GetHeightmapNormal(origin + direction * t, triangle_id) (numerics as tt_resolve_normals), both negated when
+ * dot(direction, USGNorm) > 0, then the triangle path's tail (octahedral round trip, tangent space, origin
+ * USGNorm * 1e-4 + pos, last_pdf, hits copied); _MeshData and AggTris are not read for it. A terrain record
+ * with triangle_id >= the terrain count is malformed input and ends its path (the guard of
+ * tt_resolve_normals). Without a terrain set, or without the flag, nothing changes. */
 tt_status tt_enqueue_diffuse_bounce(tt_ctx* ctx, const tt_trace_params* p, tt_ray_data* global_rays,
                                     int32_t frames_accumulated, int32_t max_bounce, uint32_t* n_next);
 /* The same enqueue with device-resident counts: reads the traced count from n_rays_dev (nullable:
@@ -911,7 +929,10 @@ tt_status tt_enqueue_diffuse_bounce_indirect(tt_ctx* ctx, const tt_trace_params*
  * scattered back to screen order: hits_out[pixel] holds exactly the RayData.hits tt_generate_primary
  * + tt_trace_closest write at GlobalRays[pixel]. Optionally each member then continues its own rays
  * (bounce 1: tt_enqueue_diffuse_bounce_indirect + tt_trace_closest_indirect on its stream) -- the
- * bounce chain never leaves the device.
+ * bounce chain never leaves the device. Members with a terrain set (tt_group_scene_upload_terrains) march it
+ * after each triangle trace (tt_trace_heightmap_hits at bounce 0, before the info texels are packed and the
+ * records gathered; tt_trace_heightmap_indirect at bounce 1) and bounce off terrain hits
+ * (TT_ENQUEUE_TERRAIN_BOUNCE); without one a frame issues exactly the launches it issued before terrains.
  *
  * Two ways to form a group, one code path after that:
  *   tt_group_create       one process drives n devices (ncclCommInitAll): the C# / Unity host shape;
@@ -971,6 +992,10 @@ tt_status tt_group_scene_upload(tt_group* g, const tt_cwbvh_node* nodes, uint32_
  * a scene with Cutout materials needs the alpha atlas before it is traced). */
 tt_status tt_group_scene_upload_alpha_atlas(tt_group* g, const uint8_t* texels, uint32_t width, uint32_t height);
 tt_status tt_group_scene_upload_texture_atlas(tt_group* g, const uint16_t* rgba_half, uint32_t width, uint32_t height);
+/* tt_scene_upload_terrains on every local member; n == 0 clears the set. With more than one slot a member's
+ * scene context lends its scene and refuses the upload itself: this call lets the borrowers go and share again. */
+tt_status tt_group_scene_upload_terrains(tt_group* g, const tt_terrain* terrains, uint32_t n,
+                                         const uint16_t* heightmap_half, uint32_t width, uint32_t height);
 /* Per-frame scene updates on every local member, between frames (AssetManager.cs:1760-1825 on each device):
  * tt_scene_update_meshdata / tt_scene_update_nodes / tt_tlas_refit of each member's scene context. The frame slots
  * borrow that scene, and the library orders each update after the traces already issued and before later ones, so

@@ -162,6 +162,17 @@ tt_status tt_terrain_occluded_host(const tt_terrain* terrains, uint32_t n, const
 /* GetHeightmapNormal(position, terrain_id). */
 tt_status tt_terrain_normal_host(const tt_terrain* terrains, uint32_t n, const uint16_t* heightmap, uint32_t w,
                                  uint32_t h, const float* position3, uint32_t terrain_id, float* normal3);
+/* The terrain rows of tt_enqueue_diffuse_bounce with TT_ENQUEUE_TERRAIN_BOUNCE, scalar: random(1, pixel), the
+ * cosine sample with the pinned sincos, the octahedral round trip, GetTangentSpace and the terrain branch of
+ * kernel_shade's diffuse subset (RayTracingShader.compute:52-84, 99-122). global_rays: the array the enqueue
+ * reads (the bounce half p selects); frame_pixels as tt_ctx_set_frame_pixels (0: off). For ray i of the launch's
+ * window survives[i] is -1 (not a terrain record: a miss or another mesh_id; out_rays[i] untouched), 0 (a
+ * terrain record whose path ends: pdf <= 0, or triangle_id >= n) or 1 (it survives; out_rays[i] is its new
+ * ray). out_rays and survives hold p->n_rays entries; nothing is compacted. */
+tt_status tt_terrain_bounce_host(const tt_terrain* terrains, uint32_t n, const uint16_t* heightmap, uint32_t w,
+                                 uint32_t h, const tt_trace_params* p, const tt_ray_data* global_rays,
+                                 int32_t frames, int32_t max_bounce, uint32_t frame_pixels, tt_ray_data* out_rays,
+                                 int32_t* survives);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,13 @@ once more over the untraced primary rays ("heightmap_open": what an open terrain
 durations of the calls (tt_timing_read), median of --reps after --warmup.
 
     python tools/terrain_bench.py [--out profiles/r08/terrain/bench.json]
+
+The enqueue leg (--enqueue) times, on the same workload, the bounce enqueue without and with
+TT_ENQUEUE_TERRAIN_BOUNCE after trace + heightmap, and tt_trace_heightmap beside tt_trace_heightmap_hits; with
+--parent-lib (the previous commit's libtruetrace_hip.so) the two libraries run alternately, one child process per
+run, --runs runs each, and the record holds the median of the runs' medians with their min - max.
+
+    python tools/terrain_bench.py --enqueue --parent-lib PATH [--out profiles/r16/terrain_bounce/bench.json]
 """
 import argparse
 import hashlib
@@ -98,6 +105,125 @@ def child(args):
     print("RESULT " + json.dumps(out))
 
 
+def enqueue_child(args):
+    """One run of the enqueue leg on the library TT_HIP_LIB names (default: this tree's)."""
+    import numpy as np
+    import torch
+
+    import ttconfigs
+    import tthip
+
+    W, H = args.width, args.height
+    n = W * H
+    scene = ttconfigs.c2_sponza()
+    terr = np.zeros(1, tthip.TERRAIN_DTYPE)
+    terr[0]["PositionOffset"] = (-60.0, -4.0, -60.0)
+    terr[0]["HeightScale"] = 1.5
+    terr[0]["TerrainDim"] = (120.0, 120.0)
+    terr[0]["HeightMap"] = (1.0, 1.0, 0.0, 0.0)
+    hmap = tthip.synthetic_heightmap(0x7E44B0, 1025, 1025)
+    eng = tthip.Engine(0)
+    eng.upload(scene)
+    eng.upload_terrains(terr, hmap)
+    new = hasattr(eng.L, "tt_trace_heightmap_hits")  # (the parent library has neither new form)
+    c2w, ip = ttconfigs.C2_VIEW.camera(W, H)
+    far = ttconfigs.FAR
+    rays = torch.zeros(2 * n * 48, dtype=torch.uint8, device="cuda:0")
+    eng.generate(rays, c2w, ip, W, H, ttconfigs.NEAR, far, device=True)
+    eng.trace(rays, n, 0, far, W, H, device=True)
+    traced = rays.clone()      # after kernel_trace
+    eng.trace_heightmap(rays, n, 0, far, W, H, device=True)
+    marched = rays.clone()     # after kernel_heightmap
+    # the hall is closed, so almost no primary ray reaches the terrain: the untraced rays marched alone give the
+    # records of an open terrain, where the flagged enqueue has terrain rows to bounce
+    eng.generate(rays, c2w, ip, W, H, ttconfigs.NEAR, far, device=True)
+    eng.trace_heightmap(rays, n, 0, far, W, H, device=True)
+    open_marched = rays.clone()
+    hits = torch.zeros(n * 4, dtype=torch.int32, device="cuda:0")
+    count = torch.zeros(1, dtype=torch.int32, device="cuda:0")
+    # two timed loops, so that the legs both libraries have run in the same sequence on either side
+    common = ["enqueue", "heightmap"]
+    added = ["enqueue_terrain_bounce", "heightmap_beside_hits", "heightmap_hits", "enqueue_open_unflagged",
+             "enqueue_open_terrain_bounce"] if new else []
+    ms = {k: [] for k in common + added}
+    survivors = {}
+    for names in (common, added):
+        for it in range((args.warmup + args.reps) if names else 0):
+            flagged = names is added
+            rays.copy_(marched)
+            torch.cuda.synchronize()
+            eng.timing_reset()
+            eng.enqueue_bounce_indirect(rays, None, n, count, 0, far, W, H, frames=1, max_bounce=3,
+                                        **({"terrain_bounce": True} if flagged else {}))
+            eng.sync()
+            survivors[names[0]] = int(count.item())
+            rays.copy_(traced)
+            eng.trace_heightmap(rays, n, 0, far, W, H, device=True, asynchronous=True)
+            if flagged:
+                rays.copy_(traced)
+                eng.trace_heightmap_hits(rays, hits, n, 0, far, W, H, asynchronous=True)
+                for k, kw in (("enqueue_open_unflagged", {}), ("enqueue_open_terrain_bounce", {"terrain_bounce": True})):
+                    rays.copy_(open_marched)
+                    eng.enqueue_bounce_indirect(rays, None, n, count, 0, far, W, H, frames=1, max_bounce=3, **kw)
+                    eng.sync()
+                    survivors[k] = int(count.item())
+            eng.sync()
+            got = eng.timing_read()
+            assert len(got) == len(names), got
+            if it >= args.warmup:
+                for k, v in zip(names, got):
+                    ms[k].append(float(v))
+    h = marched.cpu().numpy().view(tthip.RAY_DTYPE)["hits"][:n]
+    out = {"rays": n, "terrain_hits": int((h[:, 0] == tthip.TT_TERRAIN_MESH_ID).sum()), "survivors": survivors,
+           "records_sha1": hashlib.sha1(marched.cpu().numpy().tobytes()).hexdigest()}
+    for k, v in ms.items():
+        out[k] = {"ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
+    eng.close()
+    print("RESULT " + json.dumps(out))
+
+
+def enqueue_main(args):
+    sides = (["parent"] if args.parent_lib else []) + ["new"]
+    runs = {k: [] for k in sides}
+    for _ in range(args.runs):  # alternated: parent, new, parent, new, ...
+        for side in sides:
+            env = dict(os.environ)
+            env.pop("TT_HIP_LIB", None)
+            if side == "parent":
+                env["TT_HIP_LIB"] = os.path.abspath(args.parent_lib)
+            cmd = [sys.executable, os.path.abspath(__file__), "--enqueue-child", "--width", str(args.width), "--height",
+                   str(args.height), "--warmup", str(args.warmup), "--reps", str(args.reps)]
+            p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+            if p.returncode != 0:
+                sys.stderr.write(p.stdout + p.stderr)
+                return p.returncode
+            runs[side].append(json.loads([x for x in p.stdout.splitlines() if x.startswith("RESULT ")][-1][7:]))
+            sys.stderr.write(f"{side}: enqueue {runs[side][-1]['enqueue']['ms']} ms, heightmap "
+                             f"{runs[side][-1]['heightmap']['ms']} ms\n")
+            sys.stderr.flush()
+    import statistics
+
+    summary = {}
+    for side, rs in runs.items():
+        summary[side] = {}
+        for k in ("enqueue", "heightmap", "enqueue_terrain_bounce", "heightmap_beside_hits", "heightmap_hits",
+                  "enqueue_open_unflagged", "enqueue_open_terrain_bounce"):
+            v = [r[k]["ms"] for r in rs if k in r]
+            if v:
+                summary[side][k] = {"median_ms": round(statistics.median(v), 4), "min_ms": min(v), "max_ms": max(v)}
+    doc = {"scene": "C2 (262,267 tris) + one 1025x1025 terrain, 120 x 120 units, under the hall",
+           "screen": [args.width, args.height], "reps": args.reps, "runs_per_side": args.runs,
+           "what": "medians over the runs of each run's median; min - max over the runs", "summary": summary,
+           "runs": runs,
+           "records_identical": len({r["records_sha1"] for rs in runs.values() for r in rs}) == 1}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"summary": summary, "records_identical": doc["records_identical"]}, indent=1))
+    return 0 if doc["records_identical"] else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r08", "terrain", "bench.json"))
@@ -106,7 +232,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--form", choices=["persistent", "grid"], help="(child) run one form and print its result")
+    ap.add_argument("--enqueue", action="store_true", help="the enqueue leg (see the module text)")
+    ap.add_argument("--enqueue-child", action="store_true", help="(child) one run of the enqueue leg")
+    ap.add_argument("--parent-lib", help="the previous commit's libtruetrace_hip.so, run alternately with this tree's")
+    ap.add_argument("--runs", type=int, default=7)
     args = ap.parse_args()
+    if args.enqueue_child:
+        return enqueue_child(args)
+    if args.enqueue:
+        if args.out == ap.get_default("out"):
+            args.out = os.path.join(REPO, "profiles", "r16", "terrain_bounce", "bench.json")
+        return enqueue_main(args)
     if args.form:
         return child(args)
     res = {}

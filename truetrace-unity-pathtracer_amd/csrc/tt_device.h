@@ -267,6 +267,7 @@ struct TerrainArgs {
     uint32_t map_w, map_h;
     tt_ray_data* rays;           // closest hit: GlobalRays (records rewritten in place)
     uint32_t* info;              // closest hit: _PrimaryTriangleInfo, nullable
+    uint4* hits_out;             // closest hit, nullable (tt_trace_heightmap_hits): record of ray i of the launch at [i]
     unsigned char* touched;      // closest hit, STATS: per ray of the launch, 1 once its record was rewritten
     const tt_shadow_ray* srays;  // shadow: ShadowRaysBuffer (read only)
     float4* vis;                 // shadow: per ray, (1,1,1,1) not occluded so far / (0,0,0,0) occluded

@@ -522,13 +522,17 @@ static tt_status enqueue_call(tt_ctx* c, const tt_trace_params* p, const uint32_
         TT_HIP(c, stage_in(c, c->st_rays, nullptr, 2 * wh, 0, d));
         TT_HIP(c, stage_in(c, c->st_rays, rays, p->n_rays, src, d));
     }
+    // TT_ENQUEUE_TERRAIN_BOUNCE on a context with terrains: the kernel's terrain instantiation (tt_raygen.hip)
+    const uint32_t n_ter = (uint32_t)c->scene.terrains_host.size();
+    const bool bounce_off = n_ter != 0u && (p->flags & TT_ENQUEUE_TERRAIN_BOUNCE) != 0;
     uint32_t slot;
     SceneRead sr(c);
     TT_HIP(c, sr.err);
     TT_HIP(c, ring_open(c, c->timing, slot));
     TT_HIP(c, tt_launch_bounce(d, src, dst, p->n_rays, p->far_plane, p->bounce, frames, max_bounce, c->scene.tris_raw.p,
                                c->scene.mesh_raw.p, ctl_cur, c->stream, n_dev, n_next_dev, ctl_next, c->counter_words,
-                               c->frame_pixels, c->scene.terrains_host.empty() ? 0u : 1u));
+                               c->frame_pixels, n_ter ? 1u : 0u, bounce_off ? c->scene.terrains.p : nullptr,
+                               bounce_off ? n_ter : 0u, c->scene.hmap.p, c->scene.hmap_w, c->scene.hmap_h));
     c->counter_cur ^= 1u;
     TT_HIP(c, ring_close(c, c->timing, slot));
     sr.end();
@@ -604,8 +608,9 @@ void fill_terrain_args(const tt_ctx* c, uint32_t i, TerrainArgs& a) {
     a.ctl = c->ctl + c->ctl_cur;
 }
 
+// hits_out (nullable, tt_trace_heightmap_hits): the rewritten records also go to the contiguous hit stream
 tt_status heightmap_call(tt_ctx* c, const tt_trace_params* p, const uint32_t* n_dev, tt_ray_data* rays, uint32_t* info,
-                         tt_stats* stats) {
+                         tt_stats* stats, uint32_t* hits_out = nullptr) {
     if (!c) return TT_ERR_INVALID_ARG;
     TT_REFUSE_DEAD_STREAM(c);
     if (c->scene.terrains_host.empty()) return fail(c, TT_ERR_NO_SCENE, "no terrain set uploaded (tt_scene_upload_terrains)");
@@ -617,6 +622,12 @@ tt_status heightmap_call(tt_ctx* c, const tt_trace_params* p, const uint32_t* n_
     const uint64_t wh = pl.wh;
     const uint32_t off = pl.off;
     const bool dev = pl.dev, async = pl.async, want_stats = pl.want_stats;
+    if (hits_out) {  // (the refusals of trace_closest_call's hit-record stream)
+        if (!dev) return fail(c, TT_ERR_INVALID_ARG, "a hit-record stream needs TT_TRACE_DEVICE_PTRS");
+        if (want_stats) return fail(c, TT_ERR_INVALID_ARG, "tt_trace_heightmap_hits has no TT_TRACE_STATS form");
+        if (!is_device_ptr(hits_out)) return fail(c, TT_ERR_INVALID_ARG, "hits_out is not device memory");
+        if (reinterpret_cast<uintptr_t>(hits_out) % 16) return fail(c, TT_ERR_INVALID_ARG, "hits_out must be 16-byte aligned");
+    }
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (p->n_rays == 0) return TT_OK;
     if (const tt_call::Refusal r = tt_call::check_alignment(path, rays, info)) return refused(c, r);
@@ -637,6 +648,7 @@ tt_status heightmap_call(tt_ctx* c, const tt_trace_params* p, const uint32_t* n_
     std::memset(&a, 0, sizeof(a));
     a.rays = d_rays;
     a.info = d_info;
+    a.hits_out = reinterpret_cast<uint4*>(hits_out);
     a.touched = want_stats ? c->st_touched.p : nullptr;
     a.n_rays = p->n_rays;
     a.n_rays_dev = n_dev;
@@ -754,6 +766,12 @@ extern "C" {
 
 tt_status tt_trace_heightmap(tt_ctx* c, const tt_trace_params* p, tt_ray_data* rays, uint32_t* info, tt_stats* stats) {
     return heightmap_call(c, p, nullptr, rays, info, stats);
+}
+
+tt_status tt_trace_heightmap_hits(tt_ctx* c, const tt_trace_params* p, tt_ray_data* rays, uint32_t* info,
+                                  uint32_t* hits_out) {
+    if (!hits_out) return c ? fail(c, TT_ERR_INVALID_ARG, "null hits_out") : TT_ERR_INVALID_ARG;
+    return heightmap_call(c, p, nullptr, rays, info, nullptr, hits_out);
 }
 
 tt_status tt_trace_heightmap_indirect(tt_ctx* c, const tt_trace_params* p, const uint32_t* n_rays_dev, tt_ray_data* rays,

@@ -188,6 +188,7 @@ struct tt_group {
     uint32_t B = 1;  // frames per call (tt_group_config.batch)
     bool bounce = false, copy = false, info = false;
     bool direct = false;  // one rank: traced straight into the caller's outputs (tt_group_trace_frame)
+    bool terrains = false;  // the members hold a terrain set (tt_group_scene_upload_terrains): frames march it
     std::vector<Member> m;
     std::vector<uint64_t> shard_n, shard_off;  // per rank
     // rank 0's side (when this process holds it: member 0)
@@ -547,6 +548,18 @@ tt_status tt_group_scene_upload_texture_atlas(tt_group* g, const uint16_t* rgba_
     return reupload(g, [&](tt_ctx* c) { return tt_scene_upload_texture_atlas(c, rgba_half, width, height); });
 }
 
+tt_status tt_group_scene_upload_terrains(tt_group* g, const tt_terrain* terrains, uint32_t n,
+                                         const uint16_t* heightmap_half, uint32_t width, uint32_t height) {
+    if (!g) return TT_ERR_INVALID_ARG;
+    char why[256] = "";  // refused before the borrowers let go: a bad set leaves the group as it was
+    if (tt_terrain_validate(terrains, n, heightmap_half, width, height, why, sizeof(why)) != TT_OK)
+        return gfail(g, TT_ERR_INVALID_ARG, "tt_group_scene_upload_terrains: %s", why);
+    const tt_status st =
+        reupload(g, [&](tt_ctx* c) { return tt_scene_upload_terrains(c, terrains, n, heightmap_half, width, height); });
+    if (st == TT_OK) g->terrains = n != 0;
+    return st;
+}
+
 // Per-frame scene updates on every member's scene context (AssetManager.cs:1760-1825 per device): the slots
 // borrow that scene, and the library orders each update after their traces already issued and before the
 // ones issued after it (tt_ctx_share_scene), so a host calls these between frames with no synchronisation.
@@ -630,6 +643,9 @@ tt_status tt_group_trace_frame(tt_group* g, const tt_camera* cam, uint32_t* hits
             uint4* oi = !g->info ? nullptr : host_out ? g->stage.p + (size_t)B * WH : reinterpret_cast<uint4*>(info_out);
             G_TT(g, mb.ctx[s], tt_trace_closest_hits(mb.ctx[s], &p, mb.rays[s].p, reinterpret_cast<uint32_t*>(oi), nullptr,
                                                      reinterpret_cast<uint32_t*>(oh)));
+            if (g->terrains)  // kernel_heightmap after kernel_trace (RayTracingMaster.cs:973-977), before the copies
+                G_TT(g, mb.ctx[s], tt_trace_heightmap_hits(mb.ctx[s], &p, mb.rays[s].p, reinterpret_cast<uint32_t*>(oi),
+                                                           reinterpret_cast<uint32_t*>(oh)));
             if (host_out) {
                 G_HIP(g, hipMemcpyAsync(hits_out, oh, (size_t)B * WH * 16, hipMemcpyDeviceToHost, st));
                 if (g->info) G_HIP(g, hipMemcpyAsync(info_out, oi, (size_t)B * WH * 16, hipMemcpyDeviceToHost, st));
@@ -639,6 +655,10 @@ tt_status tt_group_trace_frame(tt_group* g, const tt_camera* cam, uint32_t* hits
         if (mb.n) G_TT(g, mb.ctx[s], tt_trace_closest_hits(mb.ctx[s], &p, mb.rays[s].p,
                                                            g->info ? reinterpret_cast<uint32_t*>(mb.info_full[s].p) : nullptr,
                                                            nullptr, reinterpret_cast<uint32_t*>(mb.send[s].p)));
+        if (g->terrains && mb.n)  // the terrains' records and texels, before the texels are packed and sent
+            G_TT(g, mb.ctx[s], tt_trace_heightmap_hits(mb.ctx[s], &p, mb.rays[s].p,
+                                                       g->info ? reinterpret_cast<uint32_t*>(mb.info_full[s].p) : nullptr,
+                                                       reinterpret_cast<uint32_t*>(mb.send[s].p)));
         if (g->info && mb.n) {
             hipLaunchKernelGGL(tt_group_pack_info_kernel, dim3((B * mb.n + 255u) / 256u), dim3(256), 0, st,
                                mb.info_full[s].p, mb.pixels.p, mb.n, B, WH, mb.send[s].p + (size_t)B * mb.n);
@@ -725,12 +745,15 @@ tt_status tt_group_trace_frame(tt_group* g, const tt_camera* cam, uint32_t* hits
             p.far_plane = cam->far_plane;
             p.screen_width = g->W;
             p.screen_height = HB;
-            p.flags = tflags;
+            p.flags = tflags | (g->terrains ? (uint32_t)TT_ENQUEUE_TERRAIN_BOUNCE : 0u);
             G_TT(g, mb.ctx[s], tt_enqueue_diffuse_bounce_indirect(mb.ctx[s], &p, nullptr, mb.rays[s].p,
                                                                   cam->frames_accumulated, cam->max_bounce,
                                                                   mb.count[s].p));
             p.bounce = 1;
+            p.flags = tflags;
             G_TT(g, mb.ctx[s], tt_trace_closest_indirect(mb.ctx[s], &p, mb.count[s].p, mb.rays[s].p, nullptr, nullptr));
+            if (g->terrains)
+                G_TT(g, mb.ctx[s], tt_trace_heightmap_indirect(mb.ctx[s], &p, mb.count[s].p, mb.rays[s].p, nullptr));
         }
     }
     g->frame++;

@@ -17,7 +17,8 @@ hipError_t tt_launch_bounce(tt_ray_data* rays, uint32_t src_off, uint32_t dst_of
                             int32_t cur_bounce, int32_t frames, int32_t max_bounce, const tt_cuda_triangle* tris,
                             const tt_mesh_data* md, uint32_t* counter, hipStream_t st, const uint32_t* n_dev,
                             uint32_t* n_next_dev, uint32_t* ctl_next, uint32_t ctl_next_words,
-                            uint32_t frame_pixels, uint32_t terrains);
+                            uint32_t frame_pixels, uint32_t terrains, const tt_terrain* ter = nullptr,
+                            uint32_t n_ter = 0, const uint16_t* hmap = nullptr, uint32_t hmap_w = 0, uint32_t hmap_h = 0);
 uint32_t tt_bounce_tiles(uint32_t n);
 hipError_t tt_launch_resolve(const tt_ray_data* rays, uint32_t ray_offset, uint32_t n, float far_plane,
                              const tt_cuda_triangle* tris, uint32_t n_tris, const tt_mesh_data* md, uint32_t n_mesh,

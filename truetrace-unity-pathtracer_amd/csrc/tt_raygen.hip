@@ -12,10 +12,14 @@
 //    ballot/LDS prefix inside the tile and a decoupled look-back over the preceding tiles'
 //    published counts (one 64-bit status word per tile, flag and value together), so the
 //    survivors land in source order -- deterministic, and the oracle restates the same order.
+//    tt_bounce_kernel<true> (TT_ENQUEUE_TERRAIN_BOUNCE on a context with terrains) adds kernel_shade's
+//    terrain branch (:109-111, GetHeightmapNormal as both normals) for terrain records; the compaction is
+//    the same code, and the plain instantiation keeps its registers (Terrains).
 //  * sincos in the cosine-lobe sample is pinned (sincos_pinned): HLSL leaves its precision to
 //    the driver, so both sides evaluate the same float polynomials with explicit FMAs.
 #include "tt_device.h"
 #include "tt_launch.h"
+#include "tt_terrain.h"
 
 namespace {
 
@@ -188,27 +192,44 @@ __device__ __forceinline__ float3 cosine_sample(uint32_t pixel, int32_t frames, 
 struct Ray3 {
     uint4 a, b, h;
 };
+// The terrain set as the TERRAIN instantiation of the enqueue reads it (TerrainData array, Heightmap atlas).
+struct TerrainSet {
+    const tt_terrain* terrains;
+    uint32_t n;
+    tt_ter::HeightView hmap;
+};
+// a record the TERRAIN instantiation treats as a terrain hit; one with triangle_id >= n ends its path
+__device__ __forceinline__ bool terrain_record(const uint4& h) { return h.x == TT_TERRAIN_MESH_ID; }
+
+template <bool TERRAIN>
 __device__ __forceinline__ void bounce_ray(const Ray3& R, float3 om, float pdf, const tt_cuda_triangle* tris,
-                                           const tt_mesh_data* md, uint4* o) {
+                                           const tt_mesh_data* md, const TerrainSet& ter, uint4* o) {
     const float t = __uint_as_float(R.h.z);
-    const int32_t mesh_id = (int32_t)R.h.x, tri = (int32_t)R.h.y;
-    const float u = (float)(R.h.w & 0xffffu) / 65535.0f, v = (float)(R.h.w >> 16) / 65535.0f;
-    const float* W = md[mesh_id].W2L;
-    const tt_cuda_triangle& T = tris[tri];
     const float3 dir = make_float3(__uint_as_float(R.b.x), __uint_as_float(R.b.y), __uint_as_float(R.b.z));
     const float3 org = make_float3(__uint_as_float(R.a.x), __uint_as_float(R.a.y), __uint_as_float(R.a.z));
     const float3 pos = make_float3(dir.x * t + org.x, dir.y * t + org.y, dir.z * t + org.z);
-    // Geomnorm (GetTriangleNormal) and USGNorm (RayTracingShader.compute:111-118)
-    const float3 n0 = i_octahedral_32(T.norms[0]), n1 = i_octahedral_32(T.norms[1]), n2 = i_octahedral_32(T.norms[2]);
-    const float w0 = 1.0f - u - v;
-    float3 g = mul_inv(W, make_float3(n0.x * w0 + u * n1.x + v * n2.x, n0.y * w0 + u * n1.y + v * n2.y,
-                                      n0.z * w0 + u * n1.z + v * n2.z));
-    g = normalize3(g);
-    float3 us = mul_inv(W, cross3(normalize3(make_float3(T.posedge1[0], T.posedge1[1], T.posedge1[2])),
-                                  normalize3(make_float3(T.posedge2[0], T.posedge2[1], T.posedge2[2]))));
-    us = normalize3(us);
-    us = make_float3(-us.x, -us.y, -us.z);
-    if (dot3(us, g) < 0) us = make_float3(-us.x, -us.y, -us.z);
+    float3 g, us;
+    if (TERRAIN && terrain_record(R.h)) {
+        // RayTracingShader.compute:109-111: Geomnorm = USGNorm = GetHeightmapNormal(pos, triangle_id); _MeshData and
+        // AggTris are not read (the record's mesh_id indexes nothing). triangle_id < ter.n: pass 1 checked it.
+        g = us = tt_ter::heightmap_normal(ter.hmap, ter.terrains[R.h.y], pos);
+    } else {
+        const int32_t mesh_id = (int32_t)R.h.x, tri = (int32_t)R.h.y;
+        const float u = (float)(R.h.w & 0xffffu) / 65535.0f, v = (float)(R.h.w >> 16) / 65535.0f;
+        const float* W = md[mesh_id].W2L;
+        const tt_cuda_triangle& T = tris[tri];
+        // Geomnorm (GetTriangleNormal) and USGNorm (RayTracingShader.compute:111-118)
+        const float3 n0 = i_octahedral_32(T.norms[0]), n1 = i_octahedral_32(T.norms[1]), n2 = i_octahedral_32(T.norms[2]);
+        const float w0 = 1.0f - u - v;
+        g = mul_inv(W, make_float3(n0.x * w0 + u * n1.x + v * n2.x, n0.y * w0 + u * n1.y + v * n2.y,
+                                   n0.z * w0 + u * n1.z + v * n2.z));
+        g = normalize3(g);
+        us = mul_inv(W, cross3(normalize3(make_float3(T.posedge1[0], T.posedge1[1], T.posedge1[2])),
+                               normalize3(make_float3(T.posedge2[0], T.posedge2[1], T.posedge2[2]))));
+        us = normalize3(us);
+        us = make_float3(-us.x, -us.y, -us.z);
+        if (dot3(us, g) < 0) us = make_float3(-us.x, -us.y, -us.z);
+    }
     if (dot3(dir, us) > 0.0f) {  // GotFlipped: backfacing
         us = make_float3(-us.x, -us.y, -us.z);
         g = make_float3(-g.x, -g.y, -g.z);
@@ -266,6 +287,10 @@ constexpr uint32_t TT_BOUNCE_BLOCK = 1024;                   // threads per tile
 constexpr uint32_t TT_BOUNCE_WAVES = TT_BOUNCE_BLOCK / 64;
 constexpr uint32_t TT_BOUNCE_TILE = TT_BOUNCE_BLOCK * TT_BOUNCE_K;  // 4096 rays per tile: few tickets, short look-backs
 
+// TERRAIN (TT_ENQUEUE_TERRAIN_BOUNCE on a context with terrains): a terrain record with triangle_id < ter.n
+// survives under the triangle rule and takes bounce_ray's terrain branch; a separate instantiation, so the plain
+// kernel keeps its code and registers. `terrains` (plain form): terrain records end their paths.
+template <bool TERRAIN>
 __global__ __launch_bounds__(TT_BOUNCE_BLOCK) void tt_bounce_kernel(tt_ray_data* __restrict__ rays, uint32_t src_off, uint32_t dst_off,
                                                         uint32_t n, float far_plane, int32_t cur_bounce, int32_t frames,
                                                         int32_t max_bounce, const tt_cuda_triangle* __restrict__ tris,
@@ -273,7 +298,7 @@ __global__ __launch_bounds__(TT_BOUNCE_BLOCK) void tt_bounce_kernel(tt_ray_data*
                                                         unsigned long long* __restrict__ lb, uint32_t n_tiles,
                                                         const uint32_t* __restrict__ n_dev, uint32_t* __restrict__ n_next_dev,
                                                         uint32_t* __restrict__ ctl_next, uint32_t ctl_next_words,
-                                                        uint32_t frame_pixels, uint32_t terrains) {
+                                                        uint32_t frame_pixels, uint32_t terrains, const TerrainSet ter) {
     __shared__ uint32_t s_tile, s_prefix;
     __shared__ uint32_t s_cnt[TT_BOUNCE_K][TT_BOUNCE_WAVES];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -305,7 +330,9 @@ __global__ __launch_bounds__(TT_BOUNCE_BLOCK) void tt_bounce_kernel(tt_ray_data*
             R[k].h = rp[2];
             const float t = __uint_as_float(R[k].h.z);
             // (on a context with terrains a terrain hit ends its path: its record indexes no _MeshData)
-            if (t < far_plane && (int32_t)R[k].h.y >= 0 && !(terrains && R[k].h.x == TT_TERRAIN_MESH_ID)) {
+            const bool hit = TERRAIN ? (terrain_record(R[k].h) ? R[k].h.y < ter.n : (int32_t)R[k].h.y >= 0)
+                                     : (int32_t)R[k].h.y >= 0 && !(terrains && R[k].h.x == TT_TERRAIN_MESH_ID);
+            if (t < far_plane && hit) {
                 // batched frames (tt_ctx_set_frame_pixels): PixelIndex p is pixel p mod n of frame p / n, whose
                 // random numbers are that pixel's at frames + p / n; 0: PixelIndex as-is (the reference's form)
                 uint32_t px = R[k].a.w;
@@ -357,7 +384,7 @@ __global__ __launch_bounds__(TT_BOUNCE_BLOCK) void tt_bounce_kernel(tt_ray_data*
         }
         if ((live[k] >> lane) & 1ull) {
             const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(live[k] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)live[k], 0u));
-            bounce_ray(R[k], om[k], pdf[k], tris, md, reinterpret_cast<uint4*>(rays + dst_off + slot + before + pre));
+            bounce_ray<TERRAIN>(R[k], om[k], pdf[k], tris, md, ter, reinterpret_cast<uint4*>(rays + dst_off + slot + before + pre));
         }
         slot += all;
     }
@@ -401,11 +428,14 @@ uint32_t tt_bounce_tiles(uint32_t n) { return (n + TT_BOUNCE_TILE - 1u) / TT_BOU
 // ctl_next_words words this launch zeroes for the next one.
 // n_dev (nullable): device-resident ray count, clamped to n (then n is the capacity the grid covers);
 // n_next_dev (nullable): receives the survivor count on the device.
+// terrains: the context has a terrain set (terrain records end their paths), unless ter / n_ter / hmap are passed
+// too (TT_ENQUEUE_TERRAIN_BOUNCE): then the TERRAIN instantiation runs and such rays bounce off the terrain.
 hipError_t tt_launch_bounce(tt_ray_data* rays, uint32_t src_off, uint32_t dst_off, uint32_t n, float far_plane,
                             int32_t cur_bounce, int32_t frames, int32_t max_bounce, const tt_cuda_triangle* tris,
                             const tt_mesh_data* md, uint32_t* counter, hipStream_t st, const uint32_t* n_dev,
                             uint32_t* n_next_dev, uint32_t* ctl_next, uint32_t ctl_next_words,
-                            uint32_t frame_pixels, uint32_t terrains) {
+                            uint32_t frame_pixels, uint32_t terrains, const tt_terrain* ter, uint32_t n_ter,
+                            const uint16_t* hmap, uint32_t hmap_w, uint32_t hmap_h) {
     if (n == 0) {
         if (ctl_next) {  // (this block stays zero: the next launch's block is the caller's to fill)
             const hipError_t e = hipMemsetAsync(ctl_next, 0, 4 * (size_t)ctl_next_words, st);
@@ -415,9 +445,11 @@ hipError_t tt_launch_bounce(tt_ray_data* rays, uint32_t src_off, uint32_t dst_of
         return hipSuccess;
     }
     const uint32_t tiles = tt_bounce_tiles(n);
-    hipLaunchKernelGGL(tt_bounce_kernel, dim3(tiles), dim3(TT_BOUNCE_BLOCK), 0, st, rays, src_off, dst_off, n, far_plane,
-                       cur_bounce, frames, max_bounce, tris, md, counter,
+    const bool bounce_off = ter && n_ter && hmap;
+    const TerrainSet set = bounce_off ? TerrainSet{ter, n_ter, tt_ter::HeightView{hmap, hmap_w, hmap_h}} : TerrainSet{};
+    hipLaunchKernelGGL(bounce_off ? tt_bounce_kernel<true> : tt_bounce_kernel<false>, dim3(tiles), dim3(TT_BOUNCE_BLOCK), 0,
+                       st, rays, src_off, dst_off, n, far_plane, cur_bounce, frames, max_bounce, tris, md, counter,
                        reinterpret_cast<unsigned long long*>(counter + 4), tiles, n_dev, n_next_dev, ctl_next,
-                       ctl_next_words, frame_pixels, terrains);
+                       ctl_next_words, frame_pixels, terrains, set);
     return hipGetLastError();
 }

@@ -26,23 +26,6 @@ __device__ __forceinline__ float3 i_octahedral_32(uint32_t data) {
     return normalize3(nor);
 }
 
-// GetHeightRaw / GetHeightmapNormal — CommonData.cginc:922-938
-__device__ __forceinline__ float height_raw(const tt_ter::HeightView& M, const tt_terrain& T, float x, float z) {
-    x = x - T.PositionOffset[0];
-    z = z - T.PositionOffset[2];
-    const float dx = T.TerrainDim[0], dz = T.TerrainDim[1];
-    const float u = tt_ter::min_nn(x / dx, dx / dx), v = tt_ter::min_nn(z / dz, dz / dz);
-    return tt_ter::height(M, T, u, v) * (T.HeightScale * 2.0f);
-}
-__device__ __forceinline__ float3 heightmap_normal(const tt_ter::HeightView& M, const tt_terrain& T, float3 p) {
-    const float3 c = make_float3(p.x, height_raw(M, T, p.x, p.z), p.z);
-    const float3 ox = make_float3(p.x + 0.25f, height_raw(M, T, p.x + 0.25f, p.z + 0.0f), p.z);
-    const float3 oy = make_float3(p.x, height_raw(M, T, p.x + 0.0f, p.z + 0.25f), p.z + 0.25f);
-    const float3 a = normalize3(make_float3(ox.x - c.x, ox.y - c.y, ox.z - c.z));
-    const float3 b = normalize3(make_float3(oy.x - c.x, oy.y - c.y, oy.z - c.z));
-    return normalize3(make_float3(fma_(a.y, b.z, -(a.z * b.y)), fma_(a.z, b.x, -(a.x * b.z)), fma_(a.x, b.y, -(a.y * b.x))));
-}
-
 // mul(Inverse, x) with Inverse = transpose(W2L 3x3): row r = sum_c W2L(c, r) * x_c
 __device__ __forceinline__ float3 mul_inv(const float* W, float3 x) {
     auto M = [&](int r, int c) { return W[c * 4 + r]; };
@@ -68,7 +51,7 @@ __global__ __launch_bounds__(256) void tt_resolve_kernel(const tt_ray_data* __re
     if (n_terrains != 0u && t < far_plane && h.x == TT_TERRAIN_MESH_ID && h.y < n_terrains) {
         const float3 pos = make_float3(r->direction[0] * t + r->origin[0], r->direction[1] * t + r->origin[1],
                                        r->direction[2] * t + r->origin[2]);
-        const float3 nn = heightmap_normal(hmap, terrains[h.y], pos);
+        const float3 nn = tt_ter::heightmap_normal(hmap, terrains[h.y], pos);  // (tt_terrain.h)
         o[0] = o[3] = nn.x;
         o[1] = o[4] = nn.y;
         o[2] = o[5] = nn.z;

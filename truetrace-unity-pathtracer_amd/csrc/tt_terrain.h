@@ -1,5 +1,6 @@
-// tt_terrain.h — device-side pieces shared by the heightmap kernels (tt_terrain.hip) and the attribute
-// resolve (tt_resolve.hip): the pinned Heightmap sample and the comparisons the terrain code spells out
+// tt_terrain.h — device-side pieces shared by the heightmap kernels (tt_terrain.hip), the attribute resolve
+// (tt_resolve.hip) and the bounce enqueue (tt_raygen.hip): the pinned Heightmap sample, the terrain normal and
+// the comparisons the terrain code spells out
 // (include/truetrace_hip.h: abs / max(0, q) / all(a < b) are plain IEEE comparisons, min / max NaN-ignoring).
 #ifndef TT_TERRAIN_H
 #define TT_TERRAIN_H
@@ -50,6 +51,29 @@ __device__ __forceinline__ float sample(const HeightView& M, float u, float v) {
 __device__ __forceinline__ float height(const HeightView& M, const tt_terrain& T, float u, float v) {
     return sample(M, u * (T.HeightMap[0] - T.HeightMap[2]) + T.HeightMap[2],
                   v * (T.HeightMap[1] - T.HeightMap[3]) + T.HeightMap[3]);
+}
+
+// GetHeightRaw / GetHeightmapNormal — CommonData.cginc:922-938 (normalize(v) = v * (1 / sqrt(dot(v, v)))). One copy
+// serves the attribute resolve (tt_resolve.hip) and the bounce enqueue's terrain branch (tt_raygen.hip).
+__device__ __forceinline__ float3 normalize_nn(float3 v) {
+    const float inv = 1.0f / sqrtf(__builtin_fmaf(v.z, v.z, __builtin_fmaf(v.y, v.y, v.x * v.x)));
+    return make_float3(v.x * inv, v.y * inv, v.z * inv);
+}
+__device__ __forceinline__ float height_raw(const HeightView& M, const tt_terrain& T, float x, float z) {
+    x = x - T.PositionOffset[0];
+    z = z - T.PositionOffset[2];
+    const float dx = T.TerrainDim[0], dz = T.TerrainDim[1];
+    const float u = min_nn(x / dx, dx / dx), v = min_nn(z / dz, dz / dz);
+    return height(M, T, u, v) * (T.HeightScale * 2.0f);
+}
+__device__ __forceinline__ float3 heightmap_normal(const HeightView& M, const tt_terrain& T, float3 p) {
+    const float3 c = make_float3(p.x, height_raw(M, T, p.x, p.z), p.z);
+    const float3 ox = make_float3(p.x + 0.25f, height_raw(M, T, p.x + 0.25f, p.z + 0.0f), p.z);
+    const float3 oy = make_float3(p.x, height_raw(M, T, p.x + 0.0f, p.z + 0.25f), p.z + 0.25f);
+    const float3 a = normalize_nn(make_float3(ox.x - c.x, ox.y - c.y, ox.z - c.z));
+    const float3 b = normalize_nn(make_float3(oy.x - c.x, oy.y - c.y, oy.z - c.z));
+    return normalize_nn(make_float3(__builtin_fmaf(a.y, b.z, -(a.z * b.y)), __builtin_fmaf(a.z, b.x, -(a.x * b.z)),
+                                    __builtin_fmaf(a.x, b.y, -(a.y * b.x))));
 }
 
 }  // namespace tt_ter

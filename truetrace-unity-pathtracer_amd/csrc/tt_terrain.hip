@@ -18,6 +18,8 @@
 // 1,025^2 terrain; grid vs persistent 0.055 vs 0.18 ms closest hit, 0.18 vs 0.28 ms shadow, and 1.5 vs 1.75 ms
 // for an open terrain's long marches): rays of one wave are screen neighbours whose marches are about equally
 // long, a triangle hit ends most of them after a few steps, and each refill costs a reload of the ray.
+// tt_trace_heightmap_hits: with TerrainArgs::hits_out set, a rewritten record also goes to the contiguous hit
+// stream tt_trace_closest_hits filled (ray i of the launch at [i]); both forms share write_hit.
 // Numerics: include/truetrace_hip.h; results are bit-identical to host/tt_terrain.cpp. Everything is written
 // with plain vector stores.
 #include <algorithm>
@@ -167,7 +169,9 @@ __device__ __forceinline__ void write_hit(const TerrainArgs& A, const March& m, 
         }
     }
     const uint32_t uv = d3d_f2u(u * 65535.0f) | (d3d_f2u(v * 65535.0f) << 16);  // set(), CommonData.cginc:430-434
-    reinterpret_cast<uint4*>(R)[2] = make_uint4(TT_TERRAIN_MESH_ID, A.terrain_index, __float_as_uint(t), uv);
+    const uint4 rec = make_uint4(TT_TERRAIN_MESH_ID, A.terrain_index, __float_as_uint(t), uv);
+    reinterpret_cast<uint4*>(R)[2] = rec;
+    if (A.hits_out) A.hits_out[m.ri - A.ray_offset] = rec;  // the contiguous stream tt_trace_closest_hits filled
     if (STATS) {
         unsigned char& seen = A.touched[m.ri - A.ray_offset];
         if (!seen) {

@@ -308,12 +308,105 @@ tt_status tt_terrain_occluded_host(const tt_terrain* terrains, uint32_t n, const
     return TT_OK;
 }
 
-// GetHeightmapNormal — CommonData.cginc:922-938. normalize(v) = v * (1 / sqrt(dot(v, v))).
-tt_status tt_terrain_normal_host(const tt_terrain* terrains, uint32_t n, const uint16_t* heightmap, uint32_t w, uint32_t h,
-                                 const float* position3, uint32_t terrain_id, float* normal3) {
-    if (!valid_set(terrains, n, heightmap, w, h) || !position3 || !normal3 || terrain_id >= n) return TT_ERR_INVALID_ARG;
-    const Map M = {heightmap, w, h};
-    const tt_terrain& T = terrains[terrain_id];
+}  // extern "C"
+
+namespace {
+
+inline F3 normalize(F3 a) {  // v * (1 / sqrt(dot(v, v)))
+    const float k = 1.0f / std::sqrt(std::fmaf(a.z, a.z, std::fmaf(a.y, a.y, a.x * a.x)));
+    return F3{a.x * k, a.y * k, a.z * k};
+}
+inline F3 cross(F3 a, F3 b) {
+    return {std::fmaf(a.y, b.z, -(a.z * b.y)), std::fmaf(a.z, b.x, -(a.x * b.z)), std::fmaf(a.x, b.y, -(a.y * b.x))};
+}
+inline float dot(F3 a, F3 b) { return std::fmaf(a.z, b.z, std::fmaf(a.y, b.y, a.x * b.x)); }
+
+// pcg_hash / hash_with / random() (non-ASVGF branch) — CommonData.cginc:374-389, :413-426
+inline uint32_t pcg_hash(uint32_t seed) {
+    const uint32_t state = seed * 747796405u + 2891336453u;
+    const uint32_t word = ((state >> ((state >> 28u) + 4u)) ^ state) * 277803737u;
+    return (word >> 22u) ^ word;
+}
+inline uint32_t hash_with(uint32_t seed, uint32_t hash) {
+    seed = (seed ^ 61u) ^ hash;
+    seed += seed << 3;
+    seed ^= seed >> 4;
+    seed *= 0x27d4eb2du;
+    return seed;
+}
+inline void random2(uint32_t samdim, uint32_t pixel, int32_t frames, int32_t max_bounce, int32_t cur_bounce, float& rx,
+                    float& ry) {
+    const uint32_t hash = pcg_hash((pixel * 258u + samdim) * (uint32_t)(max_bounce + 1) + (uint32_t)cur_bounce);
+    const float k = from_bits(0x2f7fffffu);  // 2.3283064365386963e-10
+    rx = (float)hash_with((uint32_t)frames, hash) * k;
+    ry = (float)hash_with((uint32_t)frames + 0xdeadbeefu, hash) * k;
+}
+
+// sin / cos of the disc-sample angle, pinned (truetrace_hip.h: the cephes single-precision minimax polynomials on
+// [-pi/4, pi/4] with explicit FMAs; |phi| > pi/4 reduced by pi/2 with a two-constant Cody-Waite step)
+inline void sincos_pinned(float phi, float& s, float& c) {
+    const bool big = absf(phi) > 0.785398185253143310546875f;
+    const float q = phi > 0.0f ? 1.0f : -1.0f;
+    const float r = big ? std::fmaf(-q, -4.37113882867379e-8f, std::fmaf(-q, 1.57079637050628662109375f, phi)) : phi;
+    const float z = r * r;
+    const float sp =
+        std::fmaf(std::fmaf(std::fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f) * z, r, r);
+    const float cp = std::fmaf(
+        std::fmaf(std::fmaf(std::fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f), z, -0.5f),
+        z, 1.0f);
+    s = big ? q * cp : sp;   // phi = q pi/2 + r: sin(phi) = q cos(r)
+    c = big ? -q * sp : cp;  //                   cos(phi) = -q sin(r)
+}
+
+// sample(): the cosine-weighted hemisphere direction and its pdf — RayTracingShader.compute:52-84
+inline F3 cosine_sample(uint32_t pixel, int32_t frames, int32_t max_bounce, int32_t cur_bounce, float& pdf) {
+    float rx, ry;
+    random2(1, pixel, frames, max_bounce, cur_bounce, rx, ry);
+    float a = 2.0f * rx - 1.0f, b = 2.0f * ry - 1.0f;
+    if (a == 0.0f) a = 0.00001f;
+    if (b == 0.0f) b = 0.00001f;
+    float phi, rr;
+    if (a * a > b * b) {
+        rr = a;
+        phi = (0.25f * 3.14159265f) * (b / a);
+    } else {
+        rr = b;
+        phi = (0.25f * 3.14159265f) * (a / b) + (0.5f * 3.14159265f);
+    }
+    float sp, cp;
+    sincos_pinned(phi, sp, cp);
+    const float dx = rr * cp, dz = rr * sp;
+    const F3 om = {dx, std::sqrt(absf(1.0f - (dx * dx + dz * dz))), dz};
+    pdf = om.y * 0.318309886548f;
+    return om;
+}
+
+// octahedral_32 / i_octahedral_32 — CommonData.cginc:840-857 (round = round-half-even)
+inline uint32_t octahedral_32(F3 nor) {
+    const float sx = nor.x >= 0.0f ? 1.0f : -1.0f, sy = nor.y >= 0.0f ? 1.0f : -1.0f;
+    const float den = nor.x * sx + nor.y * sy + absf(nor.z);
+    float x = nor.x / den, y = nor.y / den;
+    if (!(nor.z >= 0.0f)) {
+        const float ox = x;
+        x = (1.0f - (y * sy)) * sx;
+        y = (1.0f - (ox * sx)) * sy;
+    }
+    const uint32_t dx = (uint32_t)std::nearbyintf(32767.5f + x * 32767.5f);
+    const uint32_t dy = (uint32_t)std::nearbyintf(32767.5f + y * 32767.5f);
+    return dx | (dy << 16u);
+}
+inline F3 i_octahedral_32(uint32_t data) {
+    const uint32_t ix = data & 65535u, iy = (data >> 16) & 65535u;
+    const float vx = (float)ix / 32767.5f - 1.0f, vy = (float)iy / 32767.5f - 1.0f;
+    F3 nor = {vx, vy, 1.0f - absf(vx) - absf(vy)};
+    const float t = max_nn(-nor.z, 0.0f);
+    nor.x += (nor.x > 0.0f) ? -t : t;
+    nor.y += (nor.y > 0.0f) ? -t : t;
+    return normalize(nor);
+}
+
+// GetHeightmapNormal — CommonData.cginc:922-938
+F3 heightmap_normal(const tt_terrain& T, const Map& M, F3 pos) {
     auto height_raw = [&](F3 p) {  // GetHeightRaw
         p.x = p.x - T.PositionOffset[0];
         p.z = p.z - T.PositionOffset[2];
@@ -323,20 +416,85 @@ tt_status tt_terrain_normal_host(const tt_terrain* terrains, uint32_t n, const u
                                v * (T.HeightMap[1] - T.HeightMap[3]) + T.HeightMap[3]);
         return s * (T.HeightScale * 2.0f);
     };
-    auto normalize = [](F3 a) {
-        const float k = 1.0f / std::sqrt(std::fmaf(a.z, a.z, std::fmaf(a.y, a.y, a.x * a.x)));
-        return F3{a.x * k, a.y * k, a.z * k};
-    };
-    const F3 pos = {position3[0], position3[1], position3[2]};
     const F3 c = {pos.x, height_raw(pos), pos.z};
     const F3 ox = {pos.x + 0.25f, height_raw({pos.x + 0.25f, pos.y + 0.0f, pos.z + 0.0f}), pos.z};
     const F3 oy = {pos.x, height_raw({pos.x + 0.0f, pos.y + 0.0f, pos.z + 0.25f}), pos.z + 0.25f};
     const F3 a = normalize({ox.x - c.x, ox.y - c.y, ox.z - c.z}), b = normalize({oy.x - c.x, oy.y - c.y, oy.z - c.z});
-    const F3 nn = normalize({std::fmaf(a.y, b.z, -(a.z * b.y)), std::fmaf(a.z, b.x, -(a.x * b.z)),
-                             std::fmaf(a.x, b.y, -(a.y * b.x))});
+    return normalize(cross(a, b));
+}
+
+}  // namespace
+
+extern "C" {
+
+tt_status tt_terrain_normal_host(const tt_terrain* terrains, uint32_t n, const uint16_t* heightmap, uint32_t w, uint32_t h,
+                                 const float* position3, uint32_t terrain_id, float* normal3) {
+    if (!valid_set(terrains, n, heightmap, w, h) || !position3 || !normal3 || terrain_id >= n) return TT_ERR_INVALID_ARG;
+    const F3 nn = heightmap_normal(terrains[terrain_id], Map{heightmap, w, h}, {position3[0], position3[1], position3[2]});
     normal3[0] = nn.x;
     normal3[1] = nn.y;
     normal3[2] = nn.z;
+    return TT_OK;
+}
+
+// The terrain rows of the diffuse bounce enqueue (kernel_shade's next-ray subset with the terrain branch,
+// RayTracingShader.compute:52-84, 99-122, 293, 498-506): the reference of TT_ENQUEUE_TERRAIN_BOUNCE.
+tt_status tt_terrain_bounce_host(const tt_terrain* terrains, uint32_t n, const uint16_t* heightmap, uint32_t w, uint32_t h,
+                                 const tt_trace_params* p, const tt_ray_data* global_rays, int32_t frames,
+                                 int32_t max_bounce, uint32_t frame_pixels, tt_ray_data* out_rays, int32_t* survives) {
+    if (!valid_set(terrains, n, heightmap, w, h) || !p || !global_rays || !out_rays || !survives || p->bounce < 0)
+        return TT_ERR_INVALID_ARG;
+    const Map M = {heightmap, w, h};
+    const uint64_t wh = (uint64_t)p->screen_width * p->screen_height;
+    const size_t off = (p->bounce % 2 == 1) ? (size_t)wh : 0u;
+    for (uint32_t i = 0; i < p->n_rays; i++) {
+        const tt_ray_data& R = global_rays[off + i];
+        const float t = from_bits(R.hits[2]);
+        if (R.hits[0] != TT_TERRAIN_MESH_ID) {  // a miss or a triangle record: not ours
+            survives[i] = -1;
+            continue;
+        }
+        survives[i] = 0;
+        if (!(t < p->far_plane) || R.hits[1] >= n) continue;  // (malformed: triangle_id past the set) the path ends
+        // batched frames (tt_ctx_set_frame_pixels): PixelIndex p is pixel p mod n of frame p / n
+        uint32_t px = R.PixelIndex;
+        int32_t fr = frames;
+        if (frame_pixels) {
+            const uint32_t j = px / frame_pixels;
+            px -= j * frame_pixels;
+            fr += (int32_t)j;
+        }
+        float pdf;
+        const F3 om = cosine_sample(px, fr, max_bounce, p->bounce, pdf);
+        if (!(pdf > 0.0f)) continue;
+        const F3 dir = {R.direction[0], R.direction[1], R.direction[2]};
+        const F3 pos = {dir.x * t + R.origin[0], dir.y * t + R.origin[1], dir.z * t + R.origin[2]};
+        F3 g = heightmap_normal(terrains[R.hits[1]], M, pos);  // :109-111 Geomnorm = USGNorm
+        F3 us = g;
+        if (dot(dir, us) > 0.0f) {  // GotFlipped
+            us = {-us.x, -us.y, -us.z};
+            g = {-g.x, -g.y, -g.z};
+        }
+        const F3 norm = i_octahedral_32(octahedral_32(g));
+        // GetTangentSpace(norm) — CommonData.cginc:332-343
+        const F3 helper = absf(norm.x) > 0.99f ? F3{0.0f, 0.0f, 1.0f} : F3{1.0f, 0.0f, 0.0f};
+        const F3 tangent = normalize(cross(norm, helper));
+        const F3 binormal = cross(norm, tangent);
+        const F3 nd = normalize({om.x * tangent.x + om.y * norm.x + om.z * binormal.x,
+                                 om.x * tangent.y + om.y * norm.y + om.z * binormal.y,
+                                 om.x * tangent.z + om.y * norm.z + om.z * binormal.z});
+        tt_ray_data& O = out_rays[i];
+        O.origin[0] = us.x * 0.0001f + pos.x;
+        O.origin[1] = us.y * 0.0001f + pos.y;
+        O.origin[2] = us.z * 0.0001f + pos.z;
+        O.PixelIndex = R.PixelIndex;
+        O.direction[0] = nd.x;
+        O.direction[1] = nd.y;
+        O.direction[2] = nd.z;
+        O.last_pdf = pdf;
+        for (int k = 0; k < 4; k++) O.hits[k] = R.hits[k];
+        survives[i] = 1;
+    }
     return TT_OK;
 }
 

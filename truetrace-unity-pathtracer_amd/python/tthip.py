@@ -43,6 +43,7 @@ TT_TRACE_ASYNC = 1 << 4
 TT_TRACE_IGNORE_GLASS = 1 << 5       # IgnoreGlassMain (IntersectionKernels.compute:42-44)
 TT_TRACE_IGNORE_BACKFACING = 1 << 6  # IgnoreBackfacing (IntersectionKernels.compute:45-47)
 TT_TRACE_ADAPTIVE_ORDER = 1 << 7  # dequeue the previous launch's costliest tiles first (tt_order.hip)
+TT_ENQUEUE_TERRAIN_BOUNCE = 1 << 8  # tt_enqueue_diffuse_bounce(_indirect): terrain hits bounce off the terrain
 # tt_trace_last_form: which closest-hit kernel form a context's last trace launch took
 TT_TRACE_FORM_NONE, TT_TRACE_FORM_GENERIC, TT_TRACE_FORM_LEAF = 0, 1, 2
 # tt_tlas_root_form: what a TLAS's node 0 is (2: one leaf of one instance, the leaf-TLAS kernels' condition)
@@ -283,8 +284,9 @@ def scene_lib():
                                                    C.POINTER(Stats), vp]
         L.tt_terrain_occluded_host.argtypes = [vp, u32, vp, u32, u32, vp, u32, vp, C.POINTER(Stats)]
         L.tt_terrain_normal_host.argtypes = [vp, u32, vp, u32, u32, vp, u32, vp]
+        L.tt_terrain_bounce_host.argtypes = [vp, u32, vp, u32, u32, C.POINTER(TraceParams), vp, i32, i32, u32, vp, vp]
         for s in ["tt_terrain_trace_host", "tt_terrain_trace_detail_host", "tt_terrain_occluded_host",
-                  "tt_terrain_normal_host"]:
+                  "tt_terrain_normal_host", "tt_terrain_bounce_host"]:
             getattr(L, s).restype = i32
         for s in ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_scene_assemble", "tt_scene_build_get_info",
                   "tt_scene_build_copy", "tt_bvh2_build", "tt_synth_cornell", "tt_synth_soup", "tt_synth_sponza",
@@ -344,6 +346,9 @@ def hip_lib():
             L.tt_terrain_validate.argtypes = [vp, u32, vp, u32, u32, C.c_char_p, u32]
             L.tt_trace_heightmap.argtypes = [vp, C.POINTER(TraceParams), vp, vp, C.POINTER(Stats)]
             L.tt_trace_heightmap_indirect.argtypes = [vp, C.POINTER(TraceParams), vp, vp, vp]
+            if hasattr(L, "tt_trace_heightmap_hits"):
+                L.tt_trace_heightmap_hits.argtypes = [vp, C.POINTER(TraceParams), vp, vp, vp]
+                L.tt_trace_heightmap_hits.restype = i32
             L.tt_trace_shadow_heightmap.argtypes = [vp, C.POINTER(ShadowParams), vp, vp, vp, vp, vp]
             L.tt_trace_shadow_heightmap_indirect.argtypes = [vp, C.POINTER(ShadowParams), vp, vp, vp, vp, vp, vp]
             for s in ["tt_scene_upload_terrains", "tt_terrain_validate", "tt_trace_heightmap",
@@ -479,6 +484,22 @@ def terrain_normal_host(terrains, heightmap, position, terrain_id: int) -> np.nd
     _check(scene_lib().tt_terrain_normal_host(_ptr(t), len(t), _ptr(hm), hm.shape[1], hm.shape[0], _ptr(pos),
                                               int(terrain_id), _ptr(out)), "tt_terrain_normal_host")
     return out
+
+
+def terrain_bounce_host(terrains, heightmap, rays, n_rays, bounce, far_plane, width, height, frames=0, max_bounce=3,
+                        frame_pixels=0):
+    """tt_terrain_bounce_host: the scalar reference of the enqueue's terrain rows (TT_ENQUEUE_TERRAIN_BOUNCE).
+    Returns (out_rays, survives), n_rays entries each: survives -1 not a terrain record, 0 its path ends, 1 it
+    survives and out_rays[i] is its new ray (nothing is compacted)."""
+    t = np.ascontiguousarray(terrains, TERRAIN_DTYPE)
+    hm = _half_bits(heightmap)
+    p = TraceParams(n_rays=n_rays, bounce=bounce, far_plane=far_plane, screen_width=width, screen_height=height, flags=0)
+    out = np.zeros(max(1, n_rays), RAY_DTYPE)
+    sv = np.zeros(max(1, n_rays), np.int32)
+    _check(scene_lib().tt_terrain_bounce_host(_ptr(t) if len(t) else None, len(t), _ptr(hm), hm.shape[1], hm.shape[0],
+                                              C.byref(p), _ptr(rays), frames, max_bounce, frame_pixels, _ptr(out),
+                                              _ptr(sv)), "tt_terrain_bounce_host")
+    return out[:n_rays], sv[:n_rays]
 
 
 # ---------------------------------------------------------------- matrices
@@ -1194,6 +1215,18 @@ class Engine:
             self._check(st, "tt_trace_heightmap")
         return (s, st) if not check else s
 
+    def trace_heightmap_hits(self, rays, hits_out, n_rays: int, bounce: int, far_plane: float, width: int, height: int,
+                             info=None, flags: int = 0, device: bool = True, asynchronous: bool = False,
+                             check: bool = True):
+        """tt_trace_heightmap_hits: tt_trace_heightmap that also writes every record it rewrites to the contiguous
+        hit stream hits_out (the buffer tt_trace_closest_hits filled for the same rays). Device pointers."""
+        p = TraceParams(n_rays=n_rays, bounce=bounce, far_plane=far_plane, screen_width=width, screen_height=height,
+                        flags=flags | (TT_TRACE_DEVICE_PTRS if device else 0) | (TT_TRACE_ASYNC if asynchronous else 0))
+        st = self.L.tt_trace_heightmap_hits(self.h, C.byref(p), _ptr(rays), _ptr(info), _ptr(hits_out))
+        if check:
+            self._check(st, "tt_trace_heightmap_hits")
+        return st
+
     def trace_heightmap_indirect(self, rays, n_rays_dev, capacity: int, bounce: int, far_plane: float, width: int,
                                  height: int, info=None, flags: int = 0, check: bool = True):
         """tt_trace_heightmap_indirect: min(*n_rays_dev, capacity) rays; device pointers, asynchronous."""
@@ -1394,20 +1427,23 @@ class Engine:
         self._check(self.L.tt_generate_primary(self.h, C.byref(cam), _ptr(rays)), "tt_generate_primary")
 
     def enqueue_bounce(self, rays, n_rays, bounce, far_plane, width, height, frames=0, max_bounce=3,
-                       device=False) -> int:
+                       device=False, terrain_bounce: bool = False) -> int:
+        """terrain_bounce: TT_ENQUEUE_TERRAIN_BOUNCE (terrain hits bounce off the terrain instead of ending)."""
         p = TraceParams(n_rays=n_rays, bounce=bounce, far_plane=far_plane, screen_width=width, screen_height=height,
-                        flags=TT_TRACE_DEVICE_PTRS if device else 0)
+                        flags=(TT_TRACE_DEVICE_PTRS if device else 0)
+                        | (TT_ENQUEUE_TERRAIN_BOUNCE if terrain_bounce else 0))
         n = C.c_uint32()
         self._check(self.L.tt_enqueue_diffuse_bounce(self.h, C.byref(p), _ptr(rays), frames, max_bounce,
                                                      C.byref(n)), "tt_enqueue_diffuse_bounce")
         return n.value
 
     def enqueue_bounce_indirect(self, rays, n_rays_dev, capacity, n_next_dev, bounce, far_plane, width, height,
-                                frames=0, max_bounce=3, check: bool = True):
+                                frames=0, max_bounce=3, check: bool = True, terrain_bounce: bool = False):
         """tt_enqueue_diffuse_bounce_indirect: the traced count from n_rays_dev (None: capacity), the survivor
-        count written to the device uint32 n_next_dev; no synchronization."""
+        count written to the device uint32 n_next_dev; no synchronization. terrain_bounce:
+        TT_ENQUEUE_TERRAIN_BOUNCE."""
         p = TraceParams(n_rays=capacity, bounce=bounce, far_plane=far_plane, screen_width=width, screen_height=height,
-                        flags=TT_TRACE_DEVICE_PTRS)
+                        flags=TT_TRACE_DEVICE_PTRS | (TT_ENQUEUE_TERRAIN_BOUNCE if terrain_bounce else 0))
         st = self.L.tt_enqueue_diffuse_bounce_indirect(self.h, C.byref(p), _ptr(n_rays_dev), _ptr(rays), frames,
                                                        max_bounce, _ptr(n_next_dev))
         if check:
@@ -1544,6 +1580,9 @@ def _bind_group(L):
         L.tt_group_scene_update_nodes.argtypes = [vp, u32, u32, vp]
         L.tt_group_tlas_refit.argtypes = [vp, u32, vp, u32, u32]
         L.tt_group_scene_upload_texture_atlas.argtypes = [vp, vp, u32, u32]
+        if hasattr(L, "tt_group_scene_upload_terrains"):  # (absent from older variant libraries)
+            L.tt_group_scene_upload_terrains.argtypes = [vp, vp, u32, vp, u32, u32]
+            L.tt_group_scene_upload_terrains.restype = i32
         L.tt_group_sync.argtypes = [vp]
         L.tt_group_frame_rays.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(vp)]
         L.tt_group_tile_pixels.argtypes = [u32, u32, u32, u32, u32, vp, u32, C.POINTER(u32)]
@@ -1627,6 +1666,17 @@ class Group:
             t = np.ascontiguousarray(s.texture_atlas, np.float16)
             self._check(self.L.tt_group_scene_upload_texture_atlas(self.h, t.ctypes.data, t.shape[1], t.shape[0]),
                         "tt_group_scene_upload_texture_atlas")
+
+    def upload_terrains(self, terrains, heightmap=None, check: bool = True):
+        """tt_group_scene_upload_terrains: the terrain set of every local member (as Engine.upload_terrains); no
+        terrains (None or empty) clears it."""
+        t = np.zeros(0, TERRAIN_DTYPE) if terrains is None else np.ascontiguousarray(terrains, TERRAIN_DTYPE)
+        hm = None if heightmap is None else _half_bits(heightmap)
+        h, w = (0, 0) if hm is None else hm.shape
+        st = self.L.tt_group_scene_upload_terrains(self.h, _ptr(t) if len(t) else None, len(t), _ptr(hm), w, h)
+        if check:
+            self._check(st, "tt_group_scene_upload_terrains")
+        return st
 
     def trace_frame(self, hits_out, cam_to_world, cam_inv_proj, near, far, jitter=1, frames=0, max_bounce=1,
                     asynchronous=False, info_out=None):
