@@ -207,6 +207,10 @@ namespace TrueTrace.Hip
         // HOST array of 3 x n indices or null (device presort; TTStatus.Unsupported: retry with Array.Sort's lists)
         [DllImport(Lib)] public static extern unsafe TTStatus tt_object_build_device(IntPtr ctx, ref TTMeshInput mesh,
             int* presorted, uint flags, out IntPtr obj, out TTObjectBuildInfo info);
+        // The same for many meshes in one call (the builder runs all of them level by level together): presorted is null
+        // or one host list / null per mesh; all or nothing, meshStatus names every mesh the failing stage declined
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_objects_build_device(IntPtr ctx, TTMeshInput* meshes,
+            uint nMeshes, int** presorted, uint flags, IntPtr* objs, TTObjectBuildInfo* infos, TTStatus* meshStatus);
         [DllImport(Lib)] public static extern unsafe TTStatus tt_object_read(IntPtr ctx, IntPtr obj, void* nodes, void* tris,
             int* leafOfTriangle);
         [DllImport(Lib)] public static extern TTStatus tt_object_leaf_order_device(IntPtr obj, out IntPtr leafOfTriangleDev);
@@ -723,6 +727,45 @@ namespace TrueTrace.Hip
             fixed (int* p = presorted)
                 Check(Native.tt_object_build_device(m_ctx, ref mesh, p, devicePointers ? 1u : 0u, out obj, out info));
             return new TrueTraceHipObject(obj);
+        }
+
+        /// tt_objects_build_device: a scene load's meshes built into one object each in a single call, each equal to
+        /// BuildObject's. presorted: null, or per mesh BVH2Builder's three Array.Sort lists / null (device presort,
+        /// which here takes meshes of 16 triangles and fewer too). All or nothing: on a failure nothing is created and
+        /// meshStatus tells which meshes the failing stage declined (TTStatus.Unsupported: sort those and call again).
+        public unsafe TTStatus BuildObjects(TTMeshInput[] meshes, int[][] presorted, bool devicePointers,
+                                            out TrueTraceHipObject[] objects, out TTObjectBuildInfo[] infos,
+                                            out TTStatus[] meshStatus)
+        {
+            int n = meshes.Length;
+            var handles = new IntPtr[n];
+            infos = new TTObjectBuildInfo[n];
+            meshStatus = new TTStatus[n];
+            objects = null;
+            var pins = new GCHandle[n];
+            var lists = new IntPtr[n];
+            TTStatus st;
+            try
+            {
+                for (int k = 0; k < n; k++)
+                    if (presorted != null && presorted[k] != null)
+                    {
+                        pins[k] = GCHandle.Alloc(presorted[k], GCHandleType.Pinned);
+                        lists[k] = pins[k].AddrOfPinnedObject();
+                    }
+                fixed (TTMeshInput* m = meshes) fixed (IntPtr* l = lists) fixed (IntPtr* h = handles)
+                fixed (TTObjectBuildInfo* i = infos) fixed (TTStatus* ms = meshStatus)
+                    st = Native.tt_objects_build_device(m_ctx, m, (uint)n, presorted != null ? (int**)l : null,
+                                                        devicePointers ? 1u : 0u, h, i, ms);
+            }
+            finally
+            {
+                foreach (var p in pins) if (p.IsAllocated) p.Free();
+            }
+            if (st != TTStatus.Ok) return st;
+            objects = new TrueTraceHipObject[n];
+            for (int k = 0; k < n; k++) objects[k] = new TrueTraceHipObject(handles[k]);
+            return st;
         }
 
         /// SetMeshTraceBuffers for a changed object set, on the device (tt_scene_assemble_objects): `objects` in

@@ -338,6 +338,29 @@ TT_STATIC_ASSERT(sizeof(tt_object_build_info) == 48, "tt_object_build_info is 48
  * node mirror's copy. */
 tt_status tt_object_build_device(tt_ctx* ctx, const tt_mesh_input* mesh, const int32_t* presorted, uint32_t flags,
                                  tt_object** out, tt_object_build_info* info);
+/* n_meshes meshes built into n_meshes objects in one call. out[m] is, byte for byte, the object
+ * tt_object_build_device(ctx, &meshes[m], ...) makes -- nodes, triangles, traversal records, leaf_of_triangle, both info
+ * structs, the host node mirror -- and as independent: each is destroyed, assembled, read and refitted on its own. The
+ * builder runs every level of every stage for all meshes together (csrc/tt_build.hip, the forest forms), so the host
+ * waits once per level of the deepest mesh instead of once per level of every mesh; the two mesh passes are one launch
+ * each over all triangles; host meshes travel in one copy, the node mirrors come back in one.
+ *   presorted: nullable; presorted[m] a HOST list of 3 x n_m indices or NULL (mesh m is sorted on the device). Unlike
+ *          the single call, the device sorts meshes of <= 16 triangles too. presorted_on_host is 1 exactly where a list
+ *          was supplied. The device presort still declines non-finite centroids and a depth-exhausted partition above
+ *          65536, per mesh: TT_ERR_UNSUPPORTED; the caller retries with host lists for those meshes.
+ *   flags: 0 or TT_TRACE_DEVICE_PTRS, for all meshes. lossy_scale is per mesh.
+ *   infos, mesh_status: nullable, n_meshes each.
+ * All or nothing: any failure frees everything, sets every out[m] to NULL and leaves the context usable. Failures are
+ * reported by the first stage that finds one, in the order argument checks, pass 1, presort, BVH2, BVH8, pass 2 / walk:
+ * tt_last_error names the stage and the lowest failing mesh, mesh_status[m] holds TT_OK or the status that stage found
+ * for mesh m (a BVH8 failure names the meshes found at the level the collapse stopped at). Argument checks, made
+ * before any launch, TT_ERR_INVALID_ARG: n_meshes == 0, null positions or indices, n_indices not a positive multiple
+ * of 3, a supplied presorted entry out of range, 2^29 triangles or more in the call, the single call's 4 GiB limits
+ * per object. A bad index: TT_ERR_INVALID_ARG from pass 1. Synchronizes the context stream. With tt_ctx_set_timing on,
+ * the call records the single call's five tt_timing_read entries, each once for the whole batch. */
+tt_status tt_objects_build_device(tt_ctx* ctx, const tt_mesh_input* meshes, uint32_t n_meshes,
+                                  const int32_t* const* presorted, uint32_t flags, tt_object** out,
+                                  tt_object_build_info* infos, tt_status* mesh_status);
 /* Copies an object's nodes (n_nodes x 80 B), triangles (n_tris x 88 B) and leaf order (n_tris) back to the host;
  * each pointer nullable. The leaf order exists on device-built objects only: TT_ERR_INVALID_ARG for it on an
  * object of tt_object_create (nodes and tris are still copied). Synchronizes the context stream. */

@@ -4,12 +4,14 @@ C2 Sponza-shaped (262k tris) and C5 San-Miguel-shaped (10M tris). Both builds mu
 (nodes, leaf-ordered triangles, leaf order). Usage: build_bench.py [--meshes c2,c5]
 Prints one JSON document (commit under profiles/).
 
---leg object [--meshes c2,c5,c4] [--repeats 7] [--check] [--out FILE]: a mesh set to GPU-resident objects,
-(a) Blas(mesh, engine=...) + Engine.create_object (host triangle records, four trips over the bus) against
-(b) Engine.build_object (tt_object_build_device); the two alternate, wall-clock to the synchronize, medians and
-ranges of the repeats after one warm-up; (b)'s stage split from the HIP-event entries of tt_timing_read
+--leg object [--meshes c2,c5,c4] [--routes a,b,c] [--repeats 7] [--check] [--out FILE]: a mesh set to GPU-resident
+objects, (a) Blas(mesh, engine=...) + Engine.create_object (host triangle records, four trips over the bus) against
+(b) Engine.build_object per mesh (tt_object_build_device) and (c) one Engine.build_objects call over the set
+(tt_objects_build_device); the chosen routes alternate, wall-clock to the synchronize, medians and ranges of the
+repeats after one warm-up; (b)'s and (c)'s stage splits from the HIP-event entries of tt_timing_read
 (host_walk_and_rest: the wall clock outside them -- the mesh upload, allocations, the host walk). c4 is
-C4's object set: the street plane and 600 props. --check compares what (b) reads back with the host build."""
+C4's object set: the street plane and 600 props. --check compares what (b) and (c) read back with the host build.
+--routes b with TT_HIP_LIB naming another build of the library measures that build's per-object loop."""
 import argparse
 import json
 import os
@@ -56,58 +58,85 @@ def object_leg(tthip, eng, a):
     for name in a.meshes.split(","):
         meshes = _mesh_set(tthip, name)
         tris = sum(m.view().n_indices // 3 for m in meshes)
-        ta, tb = [], []
-        for rep in range(a.repeats + 1):  # the first pair warms up
-            t0 = time.perf_counter()
-            objs = [eng.create_object(tthip.Blas(m, engine=eng)) for m in meshes]
-            eng.sync()
-            t1 = time.perf_counter()
-            del objs
-            objs = [eng.build_object(m) for m in meshes]
-            eng.sync()
-            t2 = time.perf_counter()
-            on_host = sum(o.build_info.presorted_on_host for o in objs)
-            del objs
-            if rep:
-                ta.append((t1 - t0) * 1e3)
-                tb.append((t2 - t1) * 1e3)
-        eng.set_timing(True)  # the stage split of (b): five HIP-event entries per object
-        split = []
-        for _ in range(3):
-            t0 = time.perf_counter()
-            ms = []
-            for k in range(0, len(meshes), 50):  # the ring keeps 256 entries: read every 50 objects
-                eng.timing_reset()
-                objs = [eng.build_object(m) for m in meshes[k:k + 50]]
-                ms.append(eng.timing_read())
+        routes = a.routes.split(",")
+        run = {"a": lambda: [eng.create_object(tthip.Blas(m, engine=eng)) for m in meshes],
+               "b": lambda: [eng.build_object(m) for m in meshes],
+               "c": lambda: eng.build_objects(meshes)}
+        times = {r: [] for r in routes}
+        on_host = {}
+        for rep in range(a.repeats + 1):  # the first round warms up
+            for r in routes:
+                t0 = time.perf_counter()
+                objs = run[r]()
+                eng.sync()
+                t1 = time.perf_counter()
+                if r != "a":
+                    on_host[r] = sum(o.build_info.presorted_on_host for o in objs)
                 del objs
-            wall = (time.perf_counter() - t0) * 1e3
-            ms = np.concatenate(ms)
-            assert len(ms) == 5 * len(meshes), (len(ms), len(meshes))
-            st = dict(zip(STAGES, ms.reshape(-1, 5).sum(0).tolist()))
-            st["host_walk_and_rest"] = wall - sum(st.values())
-            st["wall"] = wall
-            split.append(st)
-        eng.set_timing(False)
-        stages = {k: round(float(np.median([s[k] for s in split])), 3) for k in split[0]}
+                if rep:
+                    times[r].append((t1 - t0) * 1e3)
+        row = {"set": name, "objects": len(meshes), "tris": tris, "routes": routes,
+               "library": os.environ.get("TT_HIP_LIB", "this tree")}
+        keys = {"a": "a_blas_then_create_object_ms", "b": "b_build_object_ms", "c": "c_build_objects_ms"}
+        stats = {r: _stats(times[r]) for r in routes}
+        for r in routes:
+            row[keys[r]] = stats[r]
+            row[r + "_runs_ms"] = [round(x, 3) for x in times[r]]
+            if r in on_host:
+                row[r + "_presorted_on_host"] = on_host[r]
+        for x, y in (("a", "b"), ("b", "c")):
+            if x in stats and y in stats:
+                row[f"{y}_faster_than_{x}"] = stats[y]["max"] < stats[x]["min"]
+                row[f"{x}_{y}_ranges_overlap"] = not (stats[y]["max"] < stats[x]["min"] or stats[x]["max"] < stats[y]["min"])
+                row[f"{x}_over_{y}_medians"] = round(stats[x]["median"] / stats[y]["median"], 3)
+        eng.set_timing(True)  # the stage splits: five HIP-event entries per object in (b), per call in (c)
         p2_bytes = sum(_pass2_bytes(m.view()) * (m.view().n_indices // 3) for m in meshes)
-        p2_tbs = p2_bytes / (stages["pass2_records"] * 1e-3) / 1e12
-        sa, sb = _stats(ta), _stats(tb)
-        row = {"set": name, "objects": len(meshes), "tris": tris, "presorted_on_host": on_host,
-               "a_blas_then_create_object_ms": sa, "b_build_object_ms": sb, "a_runs_ms": [round(x, 3) for x in ta],
-               "b_runs_ms": [round(x, 3) for x in tb], "ranges_overlap": not (sb["max"] < sa["min"] or sa["max"] < sb["min"]),
-               "b_faster": sb["max"] < sa["min"], "b_stages_ms": stages, "pass2_bytes": p2_bytes,
-               "pass2_TBs": round(p2_tbs, 3), "pass2_share_of_float4_copy": round(p2_tbs / COPY_TBS, 3)}
+        row["pass2_bytes"] = p2_bytes
+        for r in [r for r in routes if r != "a"]:
+            split = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                ms = []
+                if r == "b":
+                    for k in range(0, len(meshes), 50):  # the ring keeps 256 entries: read every 50 objects
+                        eng.timing_reset()
+                        objs = [eng.build_object(m) for m in meshes[k:k + 50]]
+                        ms.append(eng.timing_read())
+                        del objs
+                else:
+                    eng.timing_reset()
+                    objs = eng.build_objects(meshes)
+                    ms.append(eng.timing_read())
+                    del objs
+                wall = (time.perf_counter() - t0) * 1e3
+                ms = np.concatenate(ms)
+                assert len(ms) == 5 * (len(meshes) if r == "b" else 1), (len(ms), len(meshes))
+                st = dict(zip(STAGES, ms.reshape(-1, 5).sum(0).tolist()))
+                st["host_walk_and_rest"] = wall - sum(st.values())
+                st["wall"] = wall
+                split.append(st)
+            stages = {k: round(float(np.median([s[k] for s in split])), 3) for k in split[0]}
+            p2_tbs = p2_bytes / (stages["pass2_records"] * 1e-3) / 1e12
+            row[r + "_stages_ms"] = stages
+            row[r + "_pass2_TBs"] = round(p2_tbs, 3)
+            row[r + "_pass2_share_of_float4_copy"] = round(p2_tbs / COPY_TBS, 3)
+        eng.set_timing(False)
         if a.check:
-            same = True
-            for m in meshes:
-                host, o = tthip.Blas(m), eng.build_object(m)
-                n, t, l = o.read()
+            batch = eng.build_objects(meshes) if "c" in routes else [None] * len(meshes)
+            same = {r: True for r in routes if r != "a"}
+            for m, oc in zip(meshes, batch):
+                host = tthip.Blas(m)
                 hn, ht = host.arrays()
-                same = same and n.tobytes() == hn.tobytes() and t.tobytes() == ht.tobytes() and bool(
-                    np.array_equal(l, host.leaf_order())) and o.build_info.bvh2_depth == host.info.bvh2_depth
-                del host, o
-            row["identical_to_host_build"] = same
+                for r, o in (("b", eng.build_object(m) if "b" in routes else None), ("c", oc)):
+                    if o is None:
+                        continue
+                    n, t, l = o.read()
+                    same[r] = same[r] and n.tobytes() == hn.tobytes() and t.tobytes() == ht.tobytes() and bool(
+                        np.array_equal(l, host.leaf_order())) and o.build_info.bvh2_depth == host.info.bvh2_depth
+                    o.destroy()
+                del host
+            for r, ok in same.items():
+                row[r + "_identical_to_host_build"] = ok
         out["rows"].append(row)
         print(f"[object] {row}", file=sys.stderr, flush=True)
         del meshes
@@ -123,6 +152,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--meshes", default="c2,c5")
     ap.add_argument("--leg", default="blas", choices=["blas", "object"])
+    ap.add_argument("--routes", default="a,b,c", help="object leg: which of the routes a, b, c to run")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--out", default=None)

@@ -134,6 +134,27 @@ __device__ inline float from_ordered(uint32_t o) {
 
 constexpr int kBlock = 256;
 
+// A forest: M meshes over one concatenated primitive range, mesh m owning positions [starts[m], starts[m + 1]).
+// Every stage below runs all meshes' nodes of one level together; a single build is the forest of one mesh.
+struct Forest {
+    const int* starts;  // M + 1
+    int M;
+};
+__device__ inline int mesh_of(const Forest& F, int p) {  // the mesh that owns position p (no loads for M = 1)
+    int lo = 0, hi = F.M - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (F.starts[mid] <= p) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+// a stage's failure: the stage-wide word the host reads every level, and the mesh that owns position p
+__device__ inline void flag_mesh(int* err, int bit, int* mesh_err, const Forest& F, int p) {
+    atomicOr(err, bit);
+    atomicOr(mesh_err + mesh_of(F, p), 1);
+}
+
 // SAH cost of every split position of every live segment for one axis; per-segment argmin (lowest
 // cost, then lowest relative index) by a 64-bit atomic min. pre[p] = union of the segment's
 // positions [first, p]; sufr[n - 1 - p] = union of [p, end] (the reverse scan's output order).
@@ -200,9 +221,12 @@ struct SplitOut {
 __global__ void k_split(int S, const Seg* __restrict__ segs, const float* __restrict__ c_cost, const int* __restrict__ c_pos,
                         const Box* __restrict__ c_left, const Box* __restrict__ c_right, SplitOut* __restrict__ out,
                         Box* __restrict__ node_box, int* __restrict__ node_left, uint32_t* __restrict__ node_count,
-                        int* __restrict__ err) {
+                        int* __restrict__ err, Forest F, int level, int* __restrict__ mesh_depth,
+                        int* __restrict__ mesh_err) {
     const int s = blockIdx.x * kBlock + threadIdx.x;
     if (s >= S) return;
+    const int mesh = mesh_of(F, segs[s].first);
+    mesh_depth[mesh] = level;  // the mesh has a live segment at this level (every writer stores the same value)
     float cost = FLT_MAX;
     int split = -1, dim = -1;
     Box L = box_init(), R = box_init();
@@ -217,8 +241,9 @@ __global__ void k_split(int S, const Seg* __restrict__ segs, const float* __rest
         }
     }
     SplitOut o{split, dim, 0};
-    if (split < 0) {
+    if (split < 0) {  // the segment ends here (its positions leave every later level); its mesh fails
         atomicOr(err, 1);
+        atomicOr(mesh_err + mesh, 1);
         out[s] = o;
         return;
     }
@@ -249,6 +274,10 @@ __global__ void k_children(int S, const Seg* __restrict__ segs, const SplitOut* 
     int b = base[s];
     const int n_left = o.split - g.first, n_right = g.first + g.count - o.split;
     int2 id = make_int2(-1, -1);
+    if (o.split < 0) {  // no split (k_split flagged its mesh): no children
+        child_id[s] = id;
+        return;
+    }
     if (n_left >= 2) {
         next[b] = Seg{g.node_index, g.node_index + 2, g.first, n_left};
         id.x = b++;
@@ -281,7 +310,7 @@ __global__ void k_scatter(int n, int d, const int* __restrict__ idx, const int* 
     if (p >= n) return;
     const int s = seg[p];
     const int v = idx[p];
-    if (s < 0 || so[s].dim == d) {
+    if (s < 0 || so[s].dim == d || so[s].split < 0) {
         out[p] = v;
         return;
     }
@@ -297,6 +326,12 @@ __global__ void k_reseg(int n, int* __restrict__ seg, const SplitOut* __restrict
     if (s < 0) return;
     const int2 id = child_id[s];
     seg[p] = p < so[s].split ? id.x : id.y;
+}
+
+// every position's first segment (seg_id: the mesh's root segment, -1 for a one-primitive mesh)
+__global__ void k_seg_of_mesh(int n, Forest F, const int* __restrict__ seg_id, int* __restrict__ seg) {
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p < n) seg[p] = seg_id[mesh_of(F, p)];
 }
 
 __global__ void k_dim_of(int S, const SplitOut* __restrict__ so, int* __restrict__ dim) {
@@ -353,7 +388,8 @@ struct Dec {
 // subtree's primitive count and first leaf position (count_primitives' range)
 __global__ void k_cost8(int m, const int* __restrict__ nodes_lvl, const Box* __restrict__ box, const int* __restrict__ left,
                         const uint32_t* __restrict__ count, float* __restrict__ cost, Dec* __restrict__ dec,
-                        int* __restrict__ nprim, int* __restrict__ firstpos, int* __restrict__ err) {
+                        int* __restrict__ nprim, int* __restrict__ firstpos, int* __restrict__ err, Forest F,
+                        int* __restrict__ mesh_err) {
     const int t = blockIdx.x * kBlock + threadIdx.x;
     if (t >= m) return;
     const int v = nodes_lvl[t];
@@ -363,7 +399,7 @@ __global__ void k_cost8(int m, const int* __restrict__ nodes_lvl, const Box* __r
         nprim[v] = np;
         firstpos[v] = left[v];
         if (np != 1) {
-            atomicOr(err, 2);
+            flag_mesh(err, 2, mesh_err, F, v >> 1);  // node slot v belongs to the mesh of position v / 2
             return;
         }
         const float cl = surface_area(a) * (float)np;
@@ -431,7 +467,7 @@ struct Rec8 {
 // internal children as records of the next level.
 __global__ void k_expand8(int lo, int hi, int cap, Rec8* __restrict__ rec, int* __restrict__ n_rec, const Box* __restrict__ box,
                           const int* __restrict__ left, const uint32_t* __restrict__ count, const Dec* __restrict__ dec,
-                          const int* __restrict__ nprim, int* __restrict__ err) {
+                          const int* __restrict__ nprim, int* __restrict__ err, Forest F, int* __restrict__ mesh_err) {
     const int x = lo + blockIdx.x * kBlock + threadIdx.x;
     if (x >= hi) return;
     Rec8& R = rec[x];
@@ -463,7 +499,7 @@ __global__ void k_expand8(int lo, int hi, int cap, Rec8* __restrict__ rec, int* 
             stn[sp] = l; sti[sp] = d.dl; sp++;
         }
     }
-    if (!ok) { atomicOr(err, 4); return; }
+    if (!ok) { flag_mesh(err, 4, mesh_err, F, N >> 1); return; }
     // order_children: greedy slot assignment by octant direction costs
     const Box nb = box[N];
     const float px = (nb.mx[0] + nb.mn[0]) / 2.0f, py = (nb.mx[1] + nb.mn[1]) / 2.0f, pz = (nb.mx[2] + nb.mn[2]) / 2.0f;
@@ -498,7 +534,7 @@ __global__ void k_expand8(int lo, int hi, int cap, Rec8* __restrict__ rec, int* 
     }
     int slots[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
     for (int c = 0; c < cc; c++) {
-        if (assignment[c] < 0) { atomicOr(err, 8); return; }  // a child no slot could take (NaN boxes)
+        if (assignment[c] < 0) { flag_mesh(err, 8, mesh_err, F, N >> 1); return; }  // a child no slot could take (NaN boxes)
         slots[assignment[c]] = children[c];
     }
     int k = 0, t = 0;
@@ -509,16 +545,16 @@ __global__ void k_expand8(int lo, int hi, int cap, Rec8* __restrict__ rec, int* 
         const int ty = dec[(size_t)c * 7].type;
         if (ty == 0) {
             const int tc = nprim[c];
-            if (!(tc > 0 && tc <= 3)) { atomicOr(err, 16); return; }
+            if (!(tc > 0 && tc <= 3)) { flag_mesh(err, 16, mesh_err, F, N >> 1); return; }
             t += tc;
-            if (t > 24) { atomicOr(err, 16); return; }
+            if (t > 24) { flag_mesh(err, 16, mesh_err, F, N >> 1); return; }
         } else if (ty == 1) {
             const int o = atomicAdd(n_rec, 1);
-            if (o >= cap) { atomicOr(err, 128); return; }
+            if (o >= cap) { flag_mesh(err, 128, mesh_err, F, N >> 1); return; }
             rec[o].bvh2 = c;
             R.crec[k++] = o;
         } else {
-            atomicOr(err, 32);
+            flag_mesh(err, 32, mesh_err, F, N >> 1);
             return;
         }
     }
@@ -566,14 +602,41 @@ __device__ inline uint32_t to_byte(float x) {
     return (uint32_t)x & 0xffu;
 }
 
+// Every mesh's node total (its root record's subtree plus the root; the first M records are the roots, in mesh
+// order), their exclusive scan -- the meshes' node bases, node_base[M] the total -- and the root boxes. One block:
+// each thread sums a contiguous run of meshes, the block scans the sums.
+__global__ __launch_bounds__(kBlock) void k_mesh_totals(Forest F, const Rec8* __restrict__ rec, const Box* __restrict__ box,
+                                                        int* __restrict__ node_base, Box* __restrict__ root_box) {
+    using Scan = rocprim::block_scan<int, kBlock>;
+    __shared__ typename Scan::storage_type tmp;
+    const int per = (F.M + kBlock - 1) / kBlock;
+    const int lo = min((int)threadIdx.x * per, F.M), hi = min(lo + per, F.M);
+    int sum = 0;
+    for (int m = lo; m < hi; m++) {
+        sum += rec[m].A + 1;
+        root_box[m] = box[2 * F.starts[m]];
+    }
+    int base = 0;
+    Scan().exclusive_scan(sum, base, 0, tmp);
+    for (int m = lo; m < hi; m++) {
+        node_base[m] = base;
+        base += rec[m].A + 1;
+    }
+    if (threadIdx.x == kBlock - 1) node_base[F.M] = base;  // (the threads past the last mesh add nothing)
+}
+
 // collapse()'s node body + Aggregate (CommonVars.cs:662-688): the 80-B node at R.idx, and the leaf
-// children's primitives (count_primitives) at cwbvh_indices[R.Ct ...]
+// children's primitives (count_primitives) at cwbvh_indices[R.Ct ...]; both numbered within the record's
+// mesh, whose nodes start at node_base[mesh] and whose leaf positions start at starts[mesh]
 __global__ void k_fill8(int m, const Rec8* __restrict__ rec, const Box* __restrict__ box, const Dec* __restrict__ dec,
                         const int* __restrict__ nprim, const int* __restrict__ firstpos, const int* __restrict__ final_idx,
-                        tt_cwbvh_node* __restrict__ out, int* __restrict__ cwbvh_indices, int* __restrict__ err) {
+                        tt_cwbvh_node* __restrict__ out, int* __restrict__ cwbvh_indices, int* __restrict__ err, Forest F,
+                        const int* __restrict__ node_base, int* __restrict__ mesh_err) {
     const int x = blockIdx.x * kBlock + threadIdx.x;
     if (x >= m) return;
     const Rec8& R = rec[x];
+    const int mesh = mesh_of(F, R.bvh2 >> 1);
+    const int leaf0 = F.starts[mesh] + R.Ct;
     const Box a = box[R.bvh2];
     const float denom = 1.0f / (float)((1 << 8) - 1);
     const float ex = mathf_pow2(mathf_ceil(mathf_log2((a.mx[0] - a.mn[0]) * denom)));
@@ -583,6 +646,7 @@ __global__ void k_fill8(int m, const Rec8* __restrict__ rec, const Box* __restri
     const uint32_t ux = __float_as_uint(ex), uy = __float_as_uint(ey), uz = __float_as_uint(ez);
     if ((ux & 0x807FFFFFu) || (uy & 0x807FFFFFu) || (uz & 0x807FFFFFu)) {
         atomicOr(err, 64);
+        atomicOr(mesh_err + mesh, 1);
         return;
     }
     uint32_t meta[2] = {0u, 0u}, qlx[2] = {0u, 0u}, qhx[2] = {0u, 0u}, qly[2] = {0u, 0u}, qhy[2] = {0u, 0u},
@@ -606,7 +670,7 @@ __global__ void k_fill8(int m, const Rec8* __restrict__ rec, const Box* __restri
             mb = 0u;
             for (int j = 0; j < tc; j++) {
                 mb |= 1u << (j + 5);
-                cwbvh_indices[R.Ct + tri + j] = final_idx[f + j];
+                cwbvh_indices[leaf0 + tri + j] = final_idx[f + j];
             }
             mb |= (uint32_t)tri;
             tri += tc;
@@ -628,7 +692,7 @@ __global__ void k_fill8(int m, const Rec8* __restrict__ rec, const Box* __restri
     o.qlo_x[0] = qlx[0]; o.qlo_x[1] = qlx[1]; o.qhi_x[0] = qhx[0]; o.qhi_x[1] = qhx[1];
     o.qlo_y[0] = qly[0]; o.qlo_y[1] = qly[1]; o.qhi_y[0] = qhy[0]; o.qhi_y[1] = qhy[1];
     o.qlo_z[0] = qlz[0]; o.qlo_z[1] = qlz[1]; o.qhi_z[0] = qhz[0]; o.qhi_z[1] = qhz[1];
-    out[R.idx] = o;
+    out[node_base[mesh] + R.idx] = o;
 }
 
 // ------------------------------------------------------------------------ presort (introsort)
@@ -823,7 +887,7 @@ __global__ void k_pswap(int n3, const int* __restrict__ part, const SortPart* __
 // the pivot into its slot; children: finished here (<= 16, or heapsort at depth 0) or the next level
 __global__ void k_children_sort(int P, const SortPart* __restrict__ parts, const int2* __restrict__ res, int* __restrict__ it,
                                 const float* __restrict__ cent, int n, SortPart* __restrict__ next, int* __restrict__ n_next,
-                                int2* __restrict__ child, int* __restrict__ err) {
+                                int2* __restrict__ child, int* __restrict__ err, Forest F, int* __restrict__ mesh_err) {
     const int s = blockIdx.x * kBlock + threadIdx.x;
     if (s >= P) return;
     const SortPart q = parts[s];
@@ -843,7 +907,7 @@ __global__ void k_children_sort(int P, const SortPart* __restrict__ parts, const
         if (size <= 16) {
             small_sort(it, k, lo, hi);
         } else if (d == 0) {
-            if (size > 65536) atomicOr(err, 1);  // left to the host: one thread would take too long
+            if (size > 65536) flag_mesh(err, 1, mesh_err, F, lo - (lo / n) * n);  // left to the host: one thread would take too long
             else heap_sort(it, k, lo, hi);
         } else {
             const int o = atomicAdd(n_next, 1);
@@ -864,24 +928,39 @@ __global__ void k_repart(int n3, int* __restrict__ part, const int2* __restrict_
     part[p] = p < left ? child[s].x : (p > left ? child[s].y : -1);
 }
 
-// BVH2Builder's centroids, (max - min) / 2 + min per axis, axis-major; flags non-finite keys
+// BVH2Builder's centroids, (max - min) / 2 + min per axis, axis-major; flags non-finite keys. sorted (nullable:
+// every mesh) marks the meshes this presort sorts: the others' lists are the caller's and stay untouched.
 __global__ void k_centroids(int n, const Box* __restrict__ prims, float* __restrict__ cent, int* __restrict__ it,
-                            int* __restrict__ bad) {
+                            int* __restrict__ bad, Forest F, const unsigned char* __restrict__ sorted,
+                            int* __restrict__ mesh_err) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
+    if (sorted && !sorted[mesh_of(F, i)]) return;
     const Box b = prims[i];
     for (int d = 0; d < 3; d++) {
         const float c = (b.mx[d] - b.mn[d]) / 2.0f + b.mn[d];
         cent[(size_t)d * n + i] = c;
         it[(size_t)d * n + i] = i;
-        if (!(c - c == 0.0f)) atomicOr(bad, 1);  // NaN or infinity: the comparator is not an order there
+        if (!(c - c == 0.0f)) flag_mesh(bad, 1, mesh_err, F, i);  // NaN or infinity: the comparator is not an order there
     }
 }
 
-// the three root partitions: position p of the 3n-long index array belongs to axis p / n
-__global__ void k_part_of_axis(int n3, int n, int* __restrict__ part) {
+// the root partitions, one per (mesh, axis): position p of the 3n-long index array belongs to axis p / n and to
+// the mesh of p % n; root_id is -1 where no partition is live (a caller's list, or at most 16 elements)
+__global__ void k_part_of_root(int n3, int n, Forest F, const int* __restrict__ root_id, int* __restrict__ part) {
     const int p = blockIdx.x * kBlock + threadIdx.x;
-    if (p < n3) part[p] = p / n;
+    if (p >= n3) return;
+    const int d = p / n;
+    part[p] = root_id[d * F.M + mesh_of(F, p - d * n)];
+}
+
+// a root partition of at most 16 elements is IntroSort's small branch at once
+__global__ void k_small_roots(int P, const SortPart* __restrict__ parts, int* __restrict__ it, const float* __restrict__ cent,
+                              int n) {
+    const int s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= P) return;
+    const SortPart q = parts[s];
+    small_sort(it, axis_keys(cent, n, q.lo), q.lo, q.hi);
 }
 
 // exclusive-scan input: live children per segment (0 past the last segment, so base[S] = total)
@@ -905,13 +984,34 @@ struct NextCount {
         return status;                                         \
     } while (0)
 
-// The BVH2 stage's result, left on the device for the BVH8 stage: BVH2Nodes (boxes, left, count; 2n
-// slots) and FinalIndices.
+// A stage's failure per mesh: every flagged mesh gets `code` in mesh_status (nullable), and the stage's message
+// names the lowest of them.
+static tt_status report_meshes(hipStream_t st, const int* mesh_err_dev, int M, tt_status code, const char* what,
+                               tt_status* mesh_status) {
+    std::vector<int> f((size_t)M, 0);
+    TT_BH(hipMemcpyAsync(f.data(), mesh_err_dev, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, st));
+    TT_BH(hipStreamSynchronize(st));
+    int first = -1;
+    for (int m = 0; m < M; m++) {
+        if (!f[m]) continue;
+        if (first < 0) first = m;
+        if (mesh_status) mesh_status[m] = code;
+    }
+    std::snprintf(g_err, sizeof(g_err), "%s (mesh %d)", what, first);
+    return code;
+}
+
+// The BVH2 stage's result, left on the device for the BVH8 stage: BVH2Nodes (boxes, left, count; 2n slots, mesh
+// m's at [2 * start_m, 2 * (start_m + n_m)), child slots and leaf positions global) and FinalIndices (global
+// primitive indices).
 struct Bvh2Dev {
     DBuf<Box> box;
     DBuf<int> left, final_idx;
+    DBuf<int> per_mesh;  // one allocation for the four per-mesh arrays: starts, root segments, error flags, depths
+    int* starts = nullptr;    // M + 1
+    int* mesh_err = nullptr;  // M
     DBuf<uint32_t> count;
-    uint32_t depth = 0;
+    std::vector<uint32_t> depth;  // per mesh: the levels at which it still had a live segment
 };
 
 // position i -> Extend(identity, primitive i): what the sequential union makes of one box
@@ -919,31 +1019,49 @@ struct RootBox {
     const Box* prims;
     __device__ Box operator()(int i) const { return ExtendOp()(box_init(), prims[i]); }
 };
-__global__ void k_root_of_one(const Box* __restrict__ prims, Box* __restrict__ node_box) {
-    node_box[0] = RootBox{prims}(0);
+// BVH2Nodes[0] of every mesh: the last element of its slice of the root scan; a one-primitive mesh's root is the
+// leaf itself (BuildRecursive(0, 2, 0, 1, 0))
+__global__ void k_mesh_roots(Forest F, const Box* __restrict__ prims, const Box* __restrict__ pre, Box* __restrict__ node_box,
+                             int* __restrict__ node_left, uint32_t* __restrict__ node_count) {
+    const int m = blockIdx.x * kBlock + threadIdx.x;
+    if (m >= F.M) return;
+    const int s = F.starts[m], c = F.starts[m + 1] - s;
+    if (c >= 2) {
+        node_box[2 * s] = pre[s + c - 1];
+    } else {
+        node_box[2 * s] = RootBox{prims}(s);
+        node_left[2 * s] = s;
+        node_count[2 * s] = 1u;
+    }
 }
 
-// prims (n boxes) and presorted (3 x n) are device arrays; everything the stage makes stays on the device.
-static tt_status bvh2_stage(hipStream_t st, const Box* prims_p, int n, const int32_t* presorted, Bvh2Dev& R) {
+// prims (n boxes, n = start[M]) and presorted (3 x n, axis-major over n, global primitive indices) are device
+// arrays; start (M + 1) is a host array. Everything the stage makes stays on the device.
+static tt_status bvh2_stage(hipStream_t st, const Box* prims_p, const uint32_t* start, int M, const int32_t* presorted,
+                            Bvh2Dev& R, tt_status* mesh_status) {
+    const int n = (int)start[M];
     const size_t n2 = 2 * (size_t)n;
-    uint32_t depth = 0;
+    int depth = 0;
     TT_BH(R.box.alloc(n2));
     TT_BH(R.left.alloc(n2));
     TT_BH(R.count.alloc(n2));
     TT_BH(R.final_idx.alloc(n));
-    if (n == 1) {  // BuildRecursive(0, 2, 0, 1, 0): the root is a leaf
-        const uint32_t one = 1u;
-        TT_BH(hipMemsetAsync(R.box.p, 0, n2 * sizeof(Box), st));
-        hipLaunchKernelGGL(k_root_of_one, dim3(1), dim3(1), 0, st, prims_p, R.box.p);
-        TT_BH(hipGetLastError());
-        TT_BH(hipMemsetAsync(R.left.p, 0, n2 * sizeof(int), st));
-        TT_BH(hipMemsetAsync(R.count.p, 0, n2 * sizeof(uint32_t), st));
-        TT_BH(hipMemcpyAsync(R.count.p, &one, sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        TT_BH(hipMemcpyAsync(R.final_idx.p, presorted, sizeof(int), hipMemcpyDeviceToDevice, st));
-        TT_BH(hipStreamSynchronize(st));
-        R.depth = 0;
-        return TT_OK;
+    TT_BH(R.per_mesh.alloc(4 * (size_t)M + 1));
+    R.starts = R.per_mesh.p;
+    int* const seg_id = R.starts + M + 1;
+    R.mesh_err = seg_id + M;
+    int* const mesh_depth = R.mesh_err + M;
+    // starts, then every mesh's root segment (one primitive: the root is a leaf, no segment): one upload
+    std::vector<int> hmesh(start, start + M + 1);
+    hmesh.resize(2 * (size_t)M + 1, -1);
+    std::vector<Seg> roots;
+    for (int m = 0; m < M; m++) {
+        const int s = hmesh[m], c = hmesh[m + 1] - s;
+        if (c < 2) continue;
+        hmesh[(size_t)M + 1 + m] = (int)roots.size();
+        roots.push_back(Seg{2 * s, 2 * s + 2, s, c});
     }
+    const Forest F{R.starts, M};
     DBuf<Box> pre, sufr, c_left, c_right;
     DBuf<int> idxb[4], seg, lrank, c_pos, dimv, base, err;
     Box* box_p = R.box.p;
@@ -979,13 +1097,16 @@ static tt_status bvh2_stage(hipStream_t st, const Box* prims_p, int n, const int
     static_assert(sizeof(Box) == 24, "Box is BBMax xyz, BBMin xyz");
     for (int d = 0; d < 3; d++)
         TT_BH(hipMemcpyAsync(idx[d], presorted + (size_t)d * n, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, st));
+    TT_BH(hipMemcpyAsync(R.starts, hmesh.data(), hmesh.size() * sizeof(int), hipMemcpyHostToDevice, st));
     TT_BH(hipMemsetAsync(box_p, 0, n2 * sizeof(Box), st));  // NativeArrayOptions.ClearMemory
     TT_BH(hipMemsetAsync(nleft_p, 0, n2 * sizeof(int), st));
     TT_BH(hipMemsetAsync(ncount_p, 0, n2 * sizeof(uint32_t), st));
-    TT_BH(hipMemsetAsync(seg.p, 0, (size_t)n * sizeof(int), st));  // every position in segment 0 (the root)
     TT_BH(hipMemsetAsync(err.p, 0, sizeof(int), st));
-    const Seg root_seg{0, 2, 0, n};
-    TT_BH(hipMemcpyAsync(segs.p, &root_seg, sizeof(Seg), hipMemcpyHostToDevice, st));
+    TT_BH(hipMemsetAsync(R.mesh_err, 0, 2 * (size_t)M * sizeof(int), st));  // the error flags and the depths
+    if (!roots.empty())
+        TT_BH(hipMemcpyAsync(segs.p, roots.data(), roots.size() * sizeof(Seg), hipMemcpyHostToDevice, st));
+    // every position in its mesh's root segment: adjacent meshes never share a scan key
+    hipLaunchKernelGGL(k_seg_of_mesh, dim3(grid_of(n)), dim3(kBlock), 0, st, n, F, seg_id, seg.p);
 
     // rocPRIM temporary storage: the largest of the scans used per level (sizes depend on n only)
     auto cnt = rocprim::make_counting_iterator<int>(0);
@@ -1009,22 +1130,24 @@ static tt_status bvh2_stage(hipStream_t st, const Box* prims_p, int n, const int
         TT_BH(rocprim::exclusive_scan(nullptr, t1, nc, base.p, 0, smax + 1, rocprim::plus<int>(), st));
         tb = std::max(tb, t1);
         auto rb0 = rocprim::make_transform_iterator(cnt, RootBox{prims_p});
-        TT_BH(rocprim::inclusive_scan(nullptr, t1, rb0, pre.p, (size_t)n, ExtendOp(), st));
+        TT_BH(rocprim::inclusive_scan_by_key(nullptr, t1, seg.p, rb0, pre.p, (size_t)n, ExtendOp(),
+                                             rocprim::equal_to<int>(), st));
         tb = std::max(tb, t1);
     }
     DBuf<unsigned char> tstore;
     TT_BH(tstore.alloc(tb));
-    // root box: Extend over the primitives in index order (BVH2Builder.cs: BVH2Nodes[0].aabb). Extend keeps the
-    // earlier value on ties, so the union is an order-preserving scan with Extend itself; its last element is
-    // the root.
+    // root boxes: Extend over a mesh's primitives in index order (BVH2Builder.cs: BVH2Nodes[0].aabb). Extend keeps
+    // the earlier value on ties, so the union is an order-preserving scan with Extend itself, keyed by the mesh's
+    // root segment; the last element of a mesh's slice is its root.
     {
         size_t t = tb;
         auto rb0 = rocprim::make_transform_iterator(cnt, RootBox{prims_p});
-        TT_BH(rocprim::inclusive_scan(tstore.p, t, rb0, pre.p, (size_t)n, ExtendOp(), st));
-        TT_BH(hipMemcpyAsync(box_p, pre.p + (n - 1), sizeof(Box), hipMemcpyDeviceToDevice, st));
+        TT_BH(rocprim::inclusive_scan_by_key(tstore.p, t, seg.p, rb0, pre.p, (size_t)n, ExtendOp(),
+                                             rocprim::equal_to<int>(), st));
+        hipLaunchKernelGGL(k_mesh_roots, dim3(grid_of(M)), dim3(kBlock), 0, st, F, prims_p, pre.p, box_p, nleft_p, ncount_p);
     }
 
-    int S = 1;
+    int S = (int)roots.size(), bad = 0;
     while (S > 0) {
         depth++;  // the children created at this level sit one deeper (BuildRecursive's depth + 1)
         TT_BH(hipMemsetAsync(best.p, 0xff, 3 * (size_t)S * sizeof(unsigned long long), st));
@@ -1045,7 +1168,7 @@ static tt_status bvh2_stage(hipStream_t st, const Box* prims_p, int n, const int
                                c_left.p + (size_t)d * S, c_right.p + (size_t)d * S);
         }
         hipLaunchKernelGGL(k_split, dim3(grid_of(S)), dim3(kBlock), 0, st, S, segs.p, c_cost.p, c_pos.p, c_left.p,
-                           c_right.p, so.p, box_p, nleft_p, ncount_p, err.p);
+                           c_right.p, so.p, box_p, nleft_p, ncount_p, err.p, F, depth, mesh_depth, R.mesh_err);
         size_t t = tb;
         auto nc = rocprim::make_transform_iterator(cnt, NextCount{so.p, S});
         TT_BH(rocprim::exclusive_scan(tstore.p, t, nc, base.p, 0, (size_t)S + 1, rocprim::plus<int>(), st));
@@ -1053,7 +1176,8 @@ static tt_status bvh2_stage(hipStream_t st, const Box* prims_p, int n, const int
         TT_BH(hipMemcpyAsync(&h[0], base.p + S, sizeof(int), hipMemcpyDeviceToHost, st));
         TT_BH(hipMemcpyAsync(&h[1], err.p, sizeof(int), hipMemcpyDeviceToHost, st));
         TT_BH(hipStreamSynchronize(st));
-        if (h[1]) TT_BFAIL(TT_ERR_UNSUPPORTED, "BVH2 stage: a node has no finite SAH split");  // the C# misbehaves too
+        bad |= h[1];
+        if (bad && M == 1) break;  // (a forest goes on: the other meshes' flags are the caller's to learn)
         hipLaunchKernelGGL(k_children, dim3(grid_of(S)), dim3(kBlock), 0, st, S, segs.p, so.p, base.p, next.p,
                            child_id.p);
         hipLaunchKernelGGL(k_dim_of, dim3(grid_of(S)), dim3(kBlock), 0, st, S, so.p, dimv.p);
@@ -1073,9 +1197,12 @@ static tt_status bvh2_stage(hipStream_t st, const Box* prims_p, int n, const int
         std::swap(segs.p, next.p);
         S = h[0];
     }
+    if (bad)  // the C# misbehaves too
+        return report_meshes(st, R.mesh_err, M, TT_ERR_UNSUPPORTED, "BVH2 stage: a node has no finite SAH split", mesh_status);
+    R.depth.assign((size_t)M, 0u);
     TT_BH(hipMemcpyAsync(R.final_idx.p, idx[0], (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, st));
+    TT_BH(hipMemcpyAsync(R.depth.data(), mesh_depth, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, st));
     TT_BH(hipStreamSynchronize(st));
-    R.depth = depth;
     return TT_OK;
 }
 
@@ -1111,7 +1238,9 @@ extern "C" tt_status tt_bvh2_build_device(tt_ctx* ctx, const float* aabbs, uint3
     hipStream_t st = ctx->stream;
     DevInputs D;
     Bvh2Dev R;
-    if ((s = upload_inputs(st, aabbs, n, presorted, D)) != TT_OK || (s = bvh2_stage(st, D.prims.p, (int)n, D.pre.p, R)) != TT_OK) {
+    const uint32_t start[2] = {0u, n};
+    if ((s = upload_inputs(st, aabbs, n, presorted, D)) != TT_OK ||
+        (s = bvh2_stage(st, D.prims.p, start, 1, D.pre.p, R, nullptr)) != TT_OK) {
         ctx->err = g_err;
         return s;
     }
@@ -1121,11 +1250,26 @@ extern "C" tt_status tt_bvh2_build_device(tt_ctx* ctx, const float* aabbs, uint3
     if (node_left) TT_BH(hipMemcpyAsync(node_left, R.left.p, n2 * sizeof(int), hipMemcpyDeviceToHost, st));
     if (node_count) TT_BH(hipMemcpyAsync(node_count, R.count.p, n2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     TT_BH(hipStreamSynchronize(st));
-    if (max_depth) *max_depth = R.depth;
+    if (max_depth) *max_depth = R.depth[0];
     return TT_OK;
 }
 
-static tt_status blas_device(hipStream_t st, const Box* prims, uint32_t n, const int32_t* presorted, tt_blas_dev& out);
+static tt_status blas_device(hipStream_t st, const Box* prims, const uint32_t* start, int M, const int32_t* presorted,
+                             tt_forest_dev& out, tt_status* mesh_status);
+
+// one mesh: the forest of one
+static tt_status blas_device_one(hipStream_t st, const Box* prims, uint32_t n, const int32_t* presorted, tt_blas_dev& out) {
+    const uint32_t start[2] = {0u, n};
+    tt_forest_dev F;
+    const tt_status s = blas_device(st, prims, start, 1, presorted, F, nullptr);
+    if (s != TT_OK) return s;
+    out.nodes = std::move(F.nodes);
+    out.cwbvh_indices = std::move(F.cwbvh_indices);
+    out.n_nodes = F.node_base[1];
+    out.bvh2_depth = F.bvh2_depth[0];
+    std::memcpy(out.root_box, F.root_box.data(), sizeof(out.root_box));
+    return TT_OK;
+}
 
 static tt_status blas_host_io(tt_ctx* ctx, const float* aabbs, uint32_t n, const int32_t* presorted, tt_cwbvh_node* nodes,
                               uint32_t max_nodes, uint32_t* n_nodes, int32_t* cwbvh_indices, uint32_t* bvh2_depth) {
@@ -1137,7 +1281,7 @@ static tt_status blas_host_io(tt_ctx* ctx, const float* aabbs, uint32_t n, const
     DevInputs D;
     tt_blas_dev B;
     if ((s = upload_inputs(st, aabbs, n, presorted, D)) != TT_OK) return s;
-    if ((s = blas_device(st, D.prims.p, n, D.pre.p, B)) != TT_OK) return s;
+    if ((s = blas_device_one(st, D.prims.p, n, D.pre.p, B)) != TT_OK) return s;
     if (B.n_nodes > max_nodes) TT_BFAIL(TT_ERR_INVALID_ARG, "tt_blas_build_device: max_nodes too small");
     TT_BH(hipMemcpyAsync(nodes, B.nodes.p, (size_t)B.n_nodes * sizeof(tt_cwbvh_node), hipMemcpyDeviceToHost, st));
     TT_BH(hipMemcpyAsync(cwbvh_indices, B.cwbvh_indices.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1159,25 +1303,36 @@ extern "C" tt_status tt_blas_build_device(tt_ctx* ctx, const float* aabbs, uint3
 tt_status tt_build_blas_dev(hipStream_t st, const float* aabbs_dev, uint32_t n, const int32_t* presorted_dev,
                             tt_blas_dev& out) {
     g_err[0] = 0;
-    return blas_device(st, reinterpret_cast<const Box*>(aabbs_dev), n, presorted_dev, out);
+    return blas_device_one(st, reinterpret_cast<const Box*>(aabbs_dev), n, presorted_dev, out);
 }
 
-// BVH2 + BVH8 + Aggregate over device-resident boxes and presorted lists; the nodes, cwbvh_indices and the root
-// box (the BVH2's node 0) stay on the device.
-static tt_status blas_device(hipStream_t st, const Box* prims, uint32_t n, const int32_t* presorted, tt_blas_dev& out) {
+tt_status tt_build_blas_forest(hipStream_t st, const float* aabbs_dev, const uint32_t* start, uint32_t n_meshes,
+                               const int32_t* presorted_dev, tt_forest_dev& out, tt_status* mesh_status) {
+    g_err[0] = 0;
+    return blas_device(st, reinterpret_cast<const Box*>(aabbs_dev), start, (int)n_meshes, presorted_dev, out, mesh_status);
+}
+
+// BVH2 + BVH8 + Aggregate over device-resident boxes and presorted lists of M meshes; the nodes (mesh after mesh,
+// each numbered from 0), cwbvh_indices (global) and the root boxes (each BVH2's node 0) stay on the device.
+static tt_status blas_device(hipStream_t st, const Box* prims, const uint32_t* start, int M, const int32_t* presorted,
+                             tt_forest_dev& out, tt_status* mesh_status) {
     tt_status s;
     Bvh2Dev B;
-    if ((s = bvh2_stage(st, prims, (int)n, presorted, B)) != TT_OK) return s;
+    if ((s = bvh2_stage(st, prims, start, M, presorted, B, mesh_status)) != TT_OK) return s;
+    const uint32_t n = start[M];
     const size_t n2 = 2 * (size_t)n;
-    // BVH2 levels, root first (for the bottom-up cost pass)
+    const Forest F{B.starts, M};
+    // BVH2 levels, the M roots first (for the bottom-up cost pass)
     DBuf<int> order, cnt1, err;
     TT_BH(order.alloc(n2));
     TT_BH(cnt1.alloc(1));
     TT_BH(err.alloc(1));
     TT_BH(hipMemsetAsync(err.p, 0, sizeof(int), st));
     const int zero = 0;
-    TT_BH(hipMemcpyAsync(order.p, &zero, sizeof(int), hipMemcpyHostToDevice, st));
-    std::vector<int> lvl{0, 1};
+    std::vector<int> root_slots((size_t)M);
+    for (int m = 0; m < M; m++) root_slots[m] = 2 * (int)start[m];
+    TT_BH(hipMemcpyAsync(order.p, root_slots.data(), (size_t)M * sizeof(int), hipMemcpyHostToDevice, st));
+    std::vector<int> lvl{0, M};
     while (lvl.back() > lvl[lvl.size() - 2]) {
         const int lo = lvl[lvl.size() - 2], hi = lvl.back();
         TT_BH(hipMemcpyAsync(cnt1.p, &zero, sizeof(int), hipMemcpyHostToDevice, st));
@@ -1201,32 +1356,36 @@ static tt_status blas_device(hipStream_t st, const Box* prims, uint32_t n, const
         const int lo = lvl[L], hi = lvl[L + 1];
         if (hi > lo)
             hipLaunchKernelGGL(k_cost8, dim3(grid_of(hi - lo)), dim3(kBlock), 0, st, hi - lo, order.p + lo, B.box.p,
-                               B.left.p, B.count.p, cost.p, dec.p, nprim.p, firstpos.p, err.p);
+                               B.left.p, B.count.p, cost.p, dec.p, nprim.p, firstpos.p, err.p, F, B.mesh_err);
     }
-    // collapse: CWBVH8 levels top down (records appended per level)
-    const size_t cap = std::max<size_t>(1, (size_t)n);
+    // collapse: CWBVH8 levels top down (records appended per level), from the M root records, each numbered
+    // within its own mesh
+    const size_t cap = std::max<size_t>((size_t)M, (size_t)n);
     DBuf<Rec8> rec;
     DBuf<int> nrec;
     TT_BH(rec.alloc(cap));
     TT_BH(nrec.alloc(1));
-    Rec8 root{};
-    root.bvh2 = 0;
-    root.idx = 0;
-    root.C = 1;
-    root.Ct = 0;
-    const int one = 1;
-    TT_BH(hipMemcpyAsync(rec.p, &root, sizeof(Rec8), hipMemcpyHostToDevice, st));
-    TT_BH(hipMemcpyAsync(nrec.p, &one, sizeof(int), hipMemcpyHostToDevice, st));
-    std::vector<int> r8{0, 1};
+    std::vector<Rec8> roots((size_t)M, Rec8{});
+    for (int m = 0; m < M; m++) {
+        roots[m].bvh2 = root_slots[m];
+        roots[m].idx = 0;
+        roots[m].C = 1;
+        roots[m].Ct = 0;
+    }
+    TT_BH(hipMemcpyAsync(rec.p, roots.data(), (size_t)M * sizeof(Rec8), hipMemcpyHostToDevice, st));
+    TT_BH(hipMemcpyAsync(nrec.p, &M, sizeof(int), hipMemcpyHostToDevice, st));
+    std::vector<int> r8{0, M};
     while (r8.back() > r8[r8.size() - 2]) {
         const int lo = r8[r8.size() - 2], hi = r8.back();
         hipLaunchKernelGGL(k_expand8, dim3(grid_of(hi - lo)), dim3(kBlock), 0, st, lo, hi, (int)cap, rec.p, nrec.p, B.box.p,
-                           B.left.p, B.count.p, dec.p, nprim.p, err.p);
+                           B.left.p, B.count.p, dec.p, nprim.p, err.p, F, B.mesh_err);
         int h[2] = {0, 0};
         TT_BH(hipMemcpyAsync(&h[0], nrec.p, sizeof(int), hipMemcpyDeviceToHost, st));
         TT_BH(hipMemcpyAsync(&h[1], err.p, sizeof(int), hipMemcpyDeviceToHost, st));
         TT_BH(hipStreamSynchronize(st));
-        if (h[1]) TT_BFAIL(TT_ERR_UNSUPPORTED, "BVH8 stage: BVH8Builder.build fails on this tree");
+        if (h[1])
+            return report_meshes(st, B.mesh_err, M, TT_ERR_UNSUPPORTED, "BVH8 stage: BVH8Builder.build fails on this tree",
+                                 mesh_status);
         if ((size_t)h[0] > cap) TT_BFAIL(TT_ERR_UNSUPPORTED, "BVH8 stage: more CWBVH8 nodes than BVH2 nodes");
         r8.push_back(h[0]);
     }
@@ -1239,34 +1398,51 @@ static tt_status blas_device(hipStream_t st, const Box* prims, uint32_t n, const
         const int lo = r8[L], hi = r8[L + 1];
         if (hi > lo) hipLaunchKernelGGL(k_down8, dim3(grid_of(hi - lo)), dim3(kBlock), 0, st, lo, hi, rec.p);
     }
+    // every root knows its node total now: the meshes' node bases are their exclusive scan
+    // (one allocation, read back in one copy: the bases, then the root boxes)
+    static_assert(sizeof(Box) == 6 * sizeof(int), "a root box is {BBMax, BBMin}");
+    DBuf<int> totals;
+    TT_BH(totals.alloc(7 * (size_t)M + 1));
+    int* const node_base = totals.p;
+    Box* const root_box = reinterpret_cast<Box*>(node_base + M + 1);
+    hipLaunchKernelGGL(k_mesh_totals, dim3(1), dim3(kBlock), 0, st, F, rec.p, B.box.p, node_base, root_box);
     TT_BH(out.nodes.alloc((size_t)total));
     TT_BH(out.cwbvh_indices.alloc(n));
     TT_BH(hipMemsetAsync(out.nodes.p, 0, (size_t)total * sizeof(tt_cwbvh_node), st));
     TT_BH(hipMemsetAsync(out.cwbvh_indices.p, 0, (size_t)n * sizeof(int), st));
     hipLaunchKernelGGL(k_fill8, dim3(grid_of(total)), dim3(kBlock), 0, st, total, rec.p, B.box.p, dec.p, nprim.p,
-                       firstpos.p, B.final_idx.p, out.nodes.p, out.cwbvh_indices.p, err.p);
+                       firstpos.p, B.final_idx.p, out.nodes.p, out.cwbvh_indices.p, err.p, F, node_base, B.mesh_err);
     TT_BH(hipGetLastError());
     int e = 0;
+    std::vector<uint32_t> back(7 * (size_t)M + 1);  // the bases, then the root boxes
     TT_BH(hipMemcpyAsync(&e, err.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    TT_BH(hipMemcpyAsync(out.root_box, B.box.p, sizeof(Box), hipMemcpyDeviceToHost, st));
+    TT_BH(hipMemcpyAsync(back.data(), node_base, back.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     TT_BH(hipStreamSynchronize(st));
-    if (e) TT_BFAIL(TT_ERR_UNSUPPORTED, "BVH8 stage: a node's quantization exponent is not a power of two");
-    out.n_nodes = (uint32_t)total;
+    out.node_base.assign(back.begin(), back.begin() + M + 1);
+    out.root_box.resize(6 * (size_t)M);
+    std::memcpy(out.root_box.data(), back.data() + M + 1, 6 * (size_t)M * sizeof(float));
+    if (e)
+        return report_meshes(st, B.mesh_err, M, TT_ERR_UNSUPPORTED,
+                             "BVH8 stage: a node's quantization exponent is not a power of two", mesh_status);
+    if (out.node_base[M] != (uint32_t)total) TT_BFAIL(TT_ERR_UNSUPPORTED, "BVH8 stage: the meshes' node totals do not add up");
     out.bvh2_depth = B.depth;
     return TT_OK;
 }
 
-// The three presorts of BVH2Builder on the GPU. TT_ERR_UNSUPPORTED (the caller sorts on the host,
-// tt_bvh2_presort) when a key is not finite or a depth-exhausted partition is too large for the
-// one-thread heapsort.
-// prims (n boxes) and presorted (3 x n, the output) are device arrays.
-static tt_status presort_device(hipStream_t st, const Box* prims_p, int n, int32_t* presorted) {
+// The three presorts of BVH2Builder on the GPU, for every mesh of a forest that `sorted` marks (nullable: all).
+// TT_ERR_UNSUPPORTED (the caller sorts those meshes on the host, tt_bvh2_presort) when a key is not finite or a
+// depth-exhausted partition is too large for the one-thread heapsort; both per mesh.
+// prims (n boxes) and presorted (3 x n, axis-major over n, global indices; the output) are device arrays.
+static tt_status presort_device(hipStream_t st, const Box* prims_p, const uint32_t* start, int M,
+                                const unsigned char* sorted, int32_t* presorted, tt_status* mesh_status) {
+    const int n = (int)start[M];
     const int n3 = 3 * n;
     DBuf<float> cent;
     int* const it_p = presorted;  // sorted in place
-    DBuf<int> part, gerank, lerank, alist, blist, pk, cnt, err;
-    DBuf<SortPart> parts, next;
+    DBuf<int> part, gerank, lerank, alist, blist, pk, cnt, err, per_mesh;
+    DBuf<SortPart> parts, next, small;
     DBuf<int2> res, child;
+    DBuf<unsigned char> sorted_dev;
     const size_t pmax = (size_t)n3 / 17 + 4;  // live partitions per level (> 16 elements each)
     TT_BH(cent.alloc(n3));
     TT_BH(part.alloc(n3));
@@ -1281,21 +1457,55 @@ static tt_status presort_device(hipStream_t st, const Box* prims_p, int n, int32
     TT_BH(child.alloc(pmax));
     TT_BH(cnt.alloc(1));
     TT_BH(err.alloc(1));
+    TT_BH(per_mesh.alloc(5 * (size_t)M + 1));  // one allocation: starts, the root partitions' ids, the error flags
+    int* const starts = per_mesh.p;
+    int* const root_id = starts + M + 1;
+    int* const mesh_err = root_id + 3 * (size_t)M;
+    // Sort(length): IntroSort(0, length - 1, 2 * FloorLog2(length)), FloorLog2 = bit length; per mesh and axis. A
+    // root of at most 16 elements is the small branch at once, one element needs nothing. (starts and the root
+    // partitions' ids: one upload.)
+    std::vector<int> hmesh(start, start + M + 1);
+    hmesh.resize(4 * (size_t)M + 1, -1);
+    int* const hroot = hmesh.data() + M + 1;
+    std::vector<SortPart> roots, smalls;
+    for (int d = 0; d < 3; d++)
+        for (int m = 0; m < M; m++) {
+            const int s = hmesh[m], c = hmesh[m + 1] - s;
+            if ((sorted && !sorted[m]) || c < 2) continue;
+            int fl = 0;
+            for (int k = c; k >= 1; k /= 2) fl++;
+            const SortPart q{d * n + s, d * n + s + c - 1, 2 * fl};
+            if (c <= 16) {
+                smalls.push_back(q);
+            } else {
+                hroot[(size_t)d * M + m] = (int)roots.size();
+                roots.push_back(q);
+            }
+        }
+    TT_BH(hipMemcpyAsync(starts, hmesh.data(), hmesh.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    if (sorted) {
+        TT_BH(sorted_dev.alloc(M));
+        TT_BH(hipMemcpyAsync(sorted_dev.p, sorted, (size_t)M, hipMemcpyHostToDevice, st));
+    }
+    const Forest F{starts, M};
     TT_BH(hipMemsetAsync(err.p, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_centroids, dim3(grid_of(n)), dim3(kBlock), 0, st, n, prims_p, cent.p, it_p, err.p);
+    TT_BH(hipMemsetAsync(mesh_err, 0, (size_t)M * sizeof(int), st));
+    hipLaunchKernelGGL(k_centroids, dim3(grid_of(n)), dim3(kBlock), 0, st, n, prims_p, cent.p, it_p, err.p, F,
+                       sorted ? sorted_dev.p : nullptr, mesh_err);
     int bad = 0;
     TT_BH(hipMemcpyAsync(&bad, err.p, sizeof(int), hipMemcpyDeviceToHost, st));
     TT_BH(hipStreamSynchronize(st));
-    if (bad) TT_BFAIL(TT_ERR_UNSUPPORTED, "presort: non-finite centroid keys (host sort)");
-    if (n <= 16) TT_BFAIL(TT_ERR_UNSUPPORTED, "presort: tiny inputs are sorted on the host");
-    // Sort(length): IntroSort(0, length - 1, 2 * FloorLog2(length)), FloorLog2 = bit length
-    int fl = 0;
-    for (int m = n; m >= 1; m /= 2) fl++;
-    std::vector<SortPart> roots;
-    for (int d = 0; d < 3; d++) roots.push_back(SortPart{d * n, d * n + n - 1, 2 * fl});
+    if (bad)
+        return report_meshes(st, mesh_err, M, TT_ERR_UNSUPPORTED, "presort: non-finite centroid keys (host sort)", mesh_status);
     int P = (int)roots.size();
-    TT_BH(hipMemcpyAsync(parts.p, roots.data(), (size_t)P * sizeof(SortPart), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_part_of_axis, dim3(grid_of(n3)), dim3(kBlock), 0, st, n3, n, part.p);
+    if (P) TT_BH(hipMemcpyAsync(parts.p, roots.data(), (size_t)P * sizeof(SortPart), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_part_of_root, dim3(grid_of(n3)), dim3(kBlock), 0, st, n3, n, F, root_id, part.p);
+    if (!smalls.empty()) {
+        TT_BH(small.alloc(smalls.size()));
+        TT_BH(hipMemcpyAsync(small.p, smalls.data(), smalls.size() * sizeof(SortPart), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_small_roots, dim3(grid_of(smalls.size())), dim3(kBlock), 0, st, (int)smalls.size(), small.p, it_p,
+                           cent.p, n);
+    }
     auto cnt_it = rocprim::make_counting_iterator<int>(0);
     size_t tb = 0, t1 = 0;
     {
@@ -1311,6 +1521,7 @@ static tt_status presort_device(hipStream_t st, const Box* prims_p, int n, int32
     }
     DBuf<unsigned char> tstore;
     TT_BH(tstore.alloc(tb));
+    int too_large = 0;
     while (P > 0) {
         hipLaunchKernelGGL(k_pivot, dim3(grid_of(P)), dim3(kBlock), 0, st, P, parts.p, it_p, cent.p, n, pk.p);
         size_t t = tb;
@@ -1330,25 +1541,39 @@ static tt_status presort_device(hipStream_t st, const Box* prims_p, int n, int32
                            it_p);
         TT_BH(hipMemsetAsync(cnt.p, 0, sizeof(int), st));
         hipLaunchKernelGGL(k_children_sort, dim3(grid_of(P)), dim3(kBlock), 0, st, P, parts.p, res.p, it_p, cent.p, n,
-                           next.p, cnt.p, child.p, err.p);
+                           next.p, cnt.p, child.p, err.p, F, mesh_err);
         hipLaunchKernelGGL(k_repart, dim3(grid_of(n3)), dim3(kBlock), 0, st, n3, part.p, res.p, child.p);
         TT_BH(hipGetLastError());
         int h[2] = {0, 0};
         TT_BH(hipMemcpyAsync(&h[0], cnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
         TT_BH(hipMemcpyAsync(&h[1], err.p, sizeof(int), hipMemcpyDeviceToHost, st));
         TT_BH(hipStreamSynchronize(st));
-        if (h[1]) TT_BFAIL(TT_ERR_UNSUPPORTED, "presort: a depth-exhausted partition is too large (host sort)");
+        too_large |= h[1];
+        if (too_large && M == 1) break;  // (a forest goes on: the partition stays unsorted, the other meshes finish)
         if ((size_t)h[0] > pmax) TT_BFAIL(TT_ERR_UNSUPPORTED, "presort: too many partitions");
         std::swap(parts.p, next.p);
         P = h[0];
     }
+    if (too_large)
+        return report_meshes(st, mesh_err, M, TT_ERR_UNSUPPORTED,
+                             "presort: a depth-exhausted partition is too large (host sort)", mesh_status);
     return TT_OK;
 }
 
+tt_status tt_build_presort_forest(hipStream_t st, const float* aabbs_dev, const uint32_t* start, uint32_t n_meshes,
+                                  const unsigned char* sorted, int32_t* presorted_dev, tt_status* mesh_status) {
+    g_err[0] = 0;
+    if (!n_meshes || start[n_meshes] >= (1u << 29)) TT_BFAIL(TT_ERR_INVALID_ARG, "presort: too many primitives");
+    return presort_device(st, reinterpret_cast<const Box*>(aabbs_dev), start, (int)n_meshes, sorted, presorted_dev, mesh_status);
+}
+
+// one mesh: the forest of one, which leaves n <= 16 to the host as it always has
 tt_status tt_build_presort_dev(hipStream_t st, const float* aabbs_dev, uint32_t n, int32_t* presorted_dev) {
     g_err[0] = 0;
     if (n >= (1u << 29)) TT_BFAIL(TT_ERR_INVALID_ARG, "presort: too many primitives");
-    return presort_device(st, reinterpret_cast<const Box*>(aabbs_dev), (int)n, presorted_dev);
+    if (n <= 16) TT_BFAIL(TT_ERR_UNSUPPORTED, "presort: tiny inputs are sorted on the host");
+    const uint32_t start[2] = {0u, n};
+    return presort_device(st, reinterpret_cast<const Box*>(aabbs_dev), start, 1, nullptr, presorted_dev, nullptr);
 }
 
 extern "C" tt_status tt_bvh2_presort_device(tt_ctx* ctx, const float* aabbs, uint32_t n, int32_t* presorted) {
@@ -1364,7 +1589,7 @@ extern "C" tt_status tt_bvh2_presort_device(tt_ctx* ctx, const float* aabbs, uin
         tt_status s = upload_inputs(st, aabbs, n, nullptr, D);
         if (s != TT_OK) return s;
         TT_BH(D.pre.alloc(3 * (size_t)n));
-        if ((s = presort_device(st, D.prims.p, (int)n, D.pre.p)) != TT_OK) return s;
+        if ((s = tt_build_presort_dev(st, reinterpret_cast<const float*>(D.prims.p), n, D.pre.p)) != TT_OK) return s;
         TT_BH(hipMemcpyAsync(presorted, D.pre.p, 3 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
         TT_BH(hipStreamSynchronize(st));
         return TT_OK;

@@ -218,7 +218,7 @@ HIP_SYMBOLS = ["tt_abi_version", "tt_device_count", "tt_ctx_create", "tt_ctx_des
                "tt_terrain_validate", "tt_trace_heightmap", "tt_trace_heightmap_indirect", "tt_trace_shadow_heightmap",
                "tt_trace_shadow_heightmap_indirect", "tt_object_validate", "tt_object_create", "tt_object_get_info",
                "tt_object_destroy", "tt_scene_layout_objects", "tt_scene_layout_counts", "tt_scene_assemble_objects",
-               "tt_object_build_device", "tt_object_read", "tt_object_leaf_order_device"]
+               "tt_object_build_device", "tt_object_read", "tt_object_leaf_order_device", "tt_objects_build_device"]
 SCENE_SYMBOLS = ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_blas_free", "tt_scene_assemble",
                  "tt_scene_build_get_info", "tt_scene_build_copy", "tt_scene_build_free", "tt_pack_octahedral",
                  "tt_bvh2_build", "tt_dotnet_sort_by_key", "tt_synth_cornell", "tt_synth_soup", "tt_synth_sponza",
@@ -372,6 +372,10 @@ def hip_lib():
             L.tt_object_leaf_order_device.argtypes = [vp, C.POINTER(vp)]
             for s in ["tt_object_build_device", "tt_object_read", "tt_object_leaf_order_device"]:
                 getattr(L, s).restype = i32
+        if hasattr(L, "tt_objects_build_device"):  # (absent from older libraries)
+            L.tt_objects_build_device.argtypes = [vp, C.POINTER(MeshInput), u32, C.POINTER(vp), u32, C.POINTER(vp),
+                                                  C.POINTER(ObjectBuildInfo), C.POINTER(i32)]
+            L.tt_objects_build_device.restype = i32
         L.tt_scene_read_nodes.argtypes = [vp, u32, u32, vp]
         L.tt_scene_read_tris.argtypes = [vp, u32, u32, vp]
         L.tt_blas_refit.argtypes = [vp, C.POINTER(BlasRefitParams), vp, vp, vp]
@@ -964,6 +968,23 @@ def tlas_root_form(node0) -> int:
     return int(f.value)
 
 
+def plan_build_batches(n_tris, budget: int):
+    """How Engine.build_objects splits a mesh list into tt_objects_build_device calls: consecutive runs [lo, hi) of
+    the list, in order, each holding as many meshes as fit `budget` triangles; a mesh above the budget goes alone.
+    A pure function of the triangle counts."""
+    if budget < 1:
+        raise ValueError("the triangle budget must be positive")
+    runs, lo, held = [], 0, 0
+    for k, n in enumerate(n_tris):
+        if k > lo and held + n > budget:
+            runs.append((lo, k))
+            lo, held = k, 0
+        held += n
+    if lo < len(n_tris):
+        runs.append((lo, len(n_tris)))
+    return runs
+
+
 class SceneObject:
     """tt_object: one BLAS resident on a device (Engine.create_object). An assembly copies it, so it may be
     destroyed as soon as Engine.assemble has returned."""
@@ -1158,6 +1179,62 @@ class Engine:
             st = self.L.tt_object_build_device(self.h, C.byref(v), pre.ctypes.data, flags, C.byref(h), C.byref(info))
         self._check(st, "tt_object_build_device")
         return SceneObject(self.L, h.value, build_info=info, engine=self)
+
+    def build_objects_raw(self, views, presorted=None, flags: int = 0):
+        """tt_objects_build_device as it stands: `views` a list of MeshInput, `presorted` None or a list of (3, n)
+        int32 arrays / None per mesh. Returns (status, handles, infos, mesh_status): handles a list of ints / None."""
+        M = len(views)
+        arr = (MeshInput * max(1, M))(*views)
+        lists = (C.c_void_p * max(1, M))()
+        keep = []
+        if presorted is not None:
+            for m, p in enumerate(presorted):
+                if p is not None:
+                    keep.append(np.ascontiguousarray(p, np.int32))
+                    lists[m] = keep[-1].ctypes.data
+        out = (C.c_void_p * max(1, M))()
+        infos = (ObjectBuildInfo * max(1, M))()
+        status = (C.c_int32 * max(1, M))()
+        st = self.L.tt_objects_build_device(self.h, arr, M, lists if presorted is not None else None, int(flags), out,
+                                            infos, status)
+        return st, [out[m] for m in range(M)], [infos[m] for m in range(M)], [status[m] for m in range(M)]
+
+    def build_objects(self, meshes, lossy_scales=None, max_tris_per_call: int = 10_000_000):
+        """tt_objects_build_device: every mesh of `meshes` (Mesh or ArrayMesh) built into an object of its own, each
+        byte for byte what build_object makes of it, in as few calls as the triangle budget allows
+        (plan_build_batches). Meshes the device presort declines (mesh_status TT_ERR_UNSUPPORTED: non-finite
+        centroids, a depth-exhausted partition too large) are retried with host presorts, the others' staying on the
+        device. Returns the SceneObjects in the order of `meshes`."""
+        meshes = list(meshes)
+        views = []
+        for k, mesh in enumerate(meshes):
+            v = mesh.view()
+            v.lossy_scale[:] = (1.0, 1.0, 1.0) if lossy_scales is None else lossy_scales[k]
+            views.append(v)
+        objects = []
+        try:
+            for lo, hi in plan_build_batches([v.n_indices // 3 for v in views], max_tris_per_call):
+                vs = views[lo:hi]
+                st, hs, infos, status = self.build_objects_raw(vs)
+                if st == TT_ERR_UNSUPPORTED:
+                    S = scene_lib()
+                    pre = [None] * len(vs)
+                    for m, v in enumerate(vs):
+                        if status[m] != TT_ERR_UNSUPPORTED:
+                            continue
+                        n = v.n_indices // 3
+                        aabbs, pre[m] = np.zeros((n, 6), np.float32), np.zeros((3, n), np.int32)
+                        _check(S.tt_blas_prepare_aabbs(C.byref(v), aabbs.ctypes.data), "tt_blas_prepare_aabbs")
+                        _check(S.tt_bvh2_presort(aabbs.ctypes.data, n, pre[m].ctypes.data), "tt_bvh2_presort")
+                    st, hs, infos, status = self.build_objects_raw(vs, pre)
+                self._check(st, "tt_objects_build_device")
+                objects += [SceneObject(self.L, h, build_info=ObjectBuildInfo.from_buffer_copy(i), engine=self)
+                            for h, i in zip(hs, infos)]
+        except Exception:
+            for o in objects:
+                o.destroy()
+            raise
+        return objects
 
     def assemble(self, objects, tlas_nodes: np.ndarray, tlas: np.ndarray, meshdata: np.ndarray, materials: np.ndarray):
         """tt_scene_assemble_objects: the scene tt_scene_upload would hold for the host-concatenated arrays, gathered
