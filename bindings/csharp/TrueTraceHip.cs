@@ -230,6 +230,13 @@ namespace TrueTrace.Hip
         [DllImport(Lib)] public static extern unsafe TTStatus tt_tlas_refit(IntPtr ctx, uint nTlasNodes, float* meshAabbs,
             uint nMesh, uint flags);
         [DllImport(Lib)] public static extern unsafe TTStatus tt_scene_read_nodes(IntPtr ctx, uint first, uint count, void* nodes);
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_scene_read_tlas_indices(IntPtr ctx, uint first, uint count, int* indices);
+        // CorrectRefit + the swap of RefitTLAS (AssetManager.cs:1423-1529): a host-built TLAS installed as one
+        // mutation (flags: TT_TRACE_ASYNC), or built on the device from MeshAABBs (flags: TT_TRACE_DEVICE_PTRS).
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_scene_update_tlas(IntPtr ctx, void* tlasNodes, uint nTlasNodes,
+            int* tlasIndices, uint nTlasIndices, uint flags);
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_tlas_rebuild(IntPtr ctx, float* meshAabbs, uint nMesh, uint flags,
+            out uint nTlasNodes);
         // ParentObject.RefitMesh: vertex buffer (floats), sharedMesh.triangles, CWBVHIndicesBufferInverted.
         [DllImport(Lib)] public static extern unsafe TTStatus tt_blas_refit(IntPtr ctx, ref TTBlasRefitParams p, float* vertices,
             int* indices, int* leafOfTriangle);
@@ -283,6 +290,10 @@ namespace TrueTrace.Hip
             uint count, void* nodes);
         [DllImport(Lib)] public static extern unsafe TTStatus tt_group_tlas_refit(IntPtr group, uint nTlasNodes,
             float* meshAabbs, uint nMesh, uint flags);
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_group_tlas_rebuild(IntPtr group, float* meshAabbs, uint nMesh,
+            uint flags, out uint nTlasNodes);
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_group_scene_update_tlas(IntPtr group, void* tlasNodes,
+            uint nTlasNodes, int* tlasIndices, uint nTlasIndices, uint flags);
         [DllImport(Lib)] public static extern TTStatus tt_group_trace_frame(IntPtr group, ref TTCamera cam, IntPtr hitsOut,
             IntPtr infoOut, uint flags);
         [DllImport(Lib)] public static extern TTStatus tt_group_sync(IntPtr group);
@@ -692,6 +703,36 @@ namespace TrueTrace.Hip
                 Check(Native.tt_tlas_refit(m_ctx, (uint)nTlasNodes, b, (uint)(meshAabbs.Length / 6), 0));
         }
 
+        /// CorrectRefit + the swap in RefitTLAS (AssetManager.cs:1423-1529) on the device: a new TLAS over this
+        /// frame's MeshAABBs, installed with its TLASBVH8Indices and leaf records. Returns the new node count
+        /// (what RefitTLAS takes from now on). TTStatus.Unsupported: build on the host and call UpdateTLAS.
+        public unsafe int RebuildTLAS(float[] meshAabbs)
+        {
+            uint n;
+            fixed (float* b = meshAabbs)
+                Check(Native.tt_tlas_rebuild(m_ctx, b, (uint)(meshAabbs.Length / 6), 0, out n));
+            return (int)n;
+        }
+
+        /// The swap alone, for a TLAS CorrectRefit built on a worker thread: TLASBVH8 nodes (80 B each,
+        /// BVH8AggregatedBuffer's TLAS region) and TLASCWBVHIndexes. The arrays may be reused at once.
+        public unsafe void UpdateTLAS<TNode>(TNode[] tlasNodes, int nTlasNodes, int[] tlasIndices, bool async = false)
+            where TNode : unmanaged
+        {
+            fixed (TNode* n = tlasNodes)
+            fixed (int* i = tlasIndices)
+                Check(Native.tt_scene_update_tlas(m_ctx, n, (uint)nTlasNodes, i, (uint)tlasIndices.Length,
+                                                  async ? (uint)TTTraceFlags.Async : 0u));
+        }
+
+        /// TLASBVH8Indices [first, first + count) as the device holds them.
+        public unsafe int[] ReadTLASIndices(int first, int count)
+        {
+            var o = new int[count];
+            fixed (int* p = o) Check(Native.tt_scene_read_tlas_indices(m_ctx, (uint)first, (uint)count, p));
+            return o;
+        }
+
         /// ParentObject.RefitMesh (ParentObject.cs:750-917) for a skinned / deformable mesh: pass the
         /// vertex buffer read back from SkinnedMeshRenderer.GetVertexBuffer (floats), the mesh's
         /// triangles, CWBVHIndicesBufferInverted and the "Transform" matrix; RefitTLAS follows.
@@ -933,6 +974,20 @@ namespace TrueTrace.Hip
         {
             fixed (float* b = meshAabbs)
                 Check(Native.tt_group_tlas_refit(m_g, (uint)nTlasNodes, b, (uint)(meshAabbs.Length / 6), 0));
+        }
+        /// CorrectRefit + the swap (AssetManager.cs:1423-1529) on every device; the new TLAS node count.
+        public unsafe int RebuildTLAS(float[] meshAabbs)
+        {
+            uint n;
+            fixed (float* b = meshAabbs)
+                Check(Native.tt_group_tlas_rebuild(m_g, b, (uint)(meshAabbs.Length / 6), 0, out n));
+            return (int)n;
+        }
+        public unsafe void UpdateTLAS<TNode>(TNode[] tlasNodes, int nTlasNodes, int[] tlasIndices) where TNode : unmanaged
+        {
+            fixed (TNode* n = tlasNodes)
+            fixed (int* i = tlasIndices)
+                Check(Native.tt_group_scene_update_tlas(m_g, n, (uint)nTlasNodes, i, (uint)tlasIndices.Length, 0));
         }
 
         /// The _AlphaAtlas / decoded _TextureAtlas on every device (after SetMeshTraceBuffers).

@@ -552,6 +552,54 @@ tt_status tt_scene_read_tris(tt_ctx* ctx, uint32_t first, uint32_t count, tt_cud
  * On a frame-slot context (tt_ctx_share_blas) nodes [0, n_tlas_nodes) are its own TLAS.
  * Synchronizes the context stream. */
 tt_status tt_scene_read_nodes(tt_ctx* ctx, uint32_t first, uint32_t count, tt_cwbvh_node* out);
+/* Copies TLASBVH8Indices [first, first+count) back from HBM (a frame slot: its own). Synchronizes the
+ * context stream. */
+tt_status tt_scene_read_tlas_indices(tt_ctx* ctx, uint32_t first, uint32_t count, int32_t* out);
+
+/* TLAS rebuild, the other half of AssetManager.RefitTLAS (AssetManager.cs:1473-1530): its background task
+ * CorrectRefit (:1423-1466) rebuilds the TLAS from the current MeshAABBs and every 25th frame the result is
+ * swapped in (:1479-1529) -- new nodes (:1525), new TLASBVH8Indices (:1518), a new refit plan. A refit keeps
+ * the upload-time topology, so a scene whose instances move far traces ever larger boxes; tt_scene_update_nodes
+ * can rewrite the nodes but not TLASBVH8Indices or the leaf records derived from them, so a new topology
+ * installed through it names the wrong meshes. These two calls replace, as ONE mutation on the context stream,
+ * TLAS nodes [0, n_tlas_nodes), the whole TLASBVH8Indices and every derived leaf record; nodes
+ * [n_tlas_nodes, previous count) are zeroed, so the device arrays are byte for byte what tt_scene_upload of the
+ * host-composed arrays would hold. _MeshData, every BLAS, the triangles, materials, atlases and terrains are
+ * untouched, nothing is reallocated, and the call is NOT refused on a lender with borrowers: like
+ * tt_tlas_refit it is a TLAS-side update -- a plain borrower (tt_ctx_share_scene) sees the new TLAS, ordered
+ * against its launches by the library; frame slots (tt_ctx_share_blas) neither see it nor wait; on a frame slot
+ * it changes that slot's TLAS alone. Refused on a plain borrower. The number of mesh records cannot change:
+ * n_tlas_indices must equal the scene's count.
+ *   Capacity: the leading nodes of the scene that no validated BLAS walk reaches -- the tlas_region of an
+ * assembled scene, 2 * n_mesh in the reference's layout (AssetManager.cs:995). Every frame slot's region behind
+ * the lender's nodes has that size too, so a slot's rebuilt TLAS may have more nodes than the uploaded one.
+ *   Validation (tt_scene_update_tlas: on the host, before anything is enqueued): the TLAS-level walk over the
+ * supplied nodes, no child index leaving [0, n_tlas_nodes); every leaf slot < n_tlas_indices; leaf bits not
+ * spilling into the internal-child bits; every index in [0, n_mesh); n_tlas_nodes <= capacity. Any failure is
+ * TT_ERR_INVALID_ARG with the reason in tt_last_error, and the scene stays exactly as it was.
+ *   Afterwards tt_tlas_refit takes the new n_tlas_nodes (its plan is rebuilt at the next call; the cached
+ * per-mesh BLAS refit plans are kept), the host knows node 0 again (the root-leaf step and the leaf-TLAS
+ * kernels follow it), and tt_ctx_share_blas accepts up to the largest TLAS installed so far.
+ *
+ * tt_scene_update_tlas installs a TLAS built on the host (tt_tlas_build in truetrace_scene.h, e.g. on a worker
+ * thread as the reference does). The arrays are copied to pinned staging before the call returns -- the caller
+ * may reuse them at once -- and one kernel reads them in place. flags: TT_TRACE_ASYNC (no stream sync; host
+ * arrays are fine with it). One tt_timing_read entry when timing is on.
+ *
+ * tt_tlas_rebuild builds on the device from mesh_aabbs (n_mesh x {BBMax[3], BBMin[3]}, the array
+ * tt_tlas_refit takes; n_mesh = the scene's count; flags: TT_TRACE_DEVICE_PTRS for boxes in HBM) -- the
+ * presort, BVH2 and BVH8 stages of the device BLAS builder over the boxes -- reads the small node and index
+ * arrays back for the checks above and the host mirror, and installs them with the same kernel, sourcing the
+ * device arrays. The result is byte-identical to tt_tlas_build + tt_scene_update_tlas. Synchronizes the
+ * context stream (the builder waits on the host once per tree level). With timing on: three tt_timing_read
+ * entries -- presort, BVH2 + BVH8, install. n_tlas_nodes (nullable) receives the new count.
+ * TT_ERR_UNSUPPORTED, reason in tt_last_error, scene unchanged -- fall back to tt_tlas_build +
+ * tt_scene_update_tlas -- when the presort declines (non-finite centroids, a depth-exhausted partition above
+ * 65536), where the reference's BVH8Builder fails, or when the result does not fit the region. */
+tt_status tt_scene_update_tlas(tt_ctx* ctx, const tt_cwbvh_node* tlas_nodes, uint32_t n_tlas_nodes,
+                               const int32_t* tlas_indices, uint32_t n_tlas_indices, uint32_t flags);
+tt_status tt_tlas_rebuild(tt_ctx* ctx, const float* mesh_aabbs, uint32_t n_mesh, uint32_t flags,
+                          uint32_t* n_tlas_nodes);
 
 /* Makes `dst` trace `src`'s scene: no copy, the device buffers of src's last tt_scene_upload (and its
  * atlases) are read by dst's launches on dst's own stream. For several contexts tracing one scene
@@ -1027,6 +1075,14 @@ tt_status tt_group_scene_update_meshdata(tt_group* g, uint32_t first, uint32_t c
 tt_status tt_group_scene_update_nodes(tt_group* g, uint32_t first, uint32_t count, const tt_cwbvh_node* nodes);
 tt_status tt_group_tlas_refit(tt_group* g, uint32_t n_tlas_nodes, const float* mesh_aabbs, uint32_t n_mesh,
                               uint32_t flags);
+/* tt_tlas_rebuild / tt_scene_update_tlas of each local member's scene context, between frames like the calls
+ * above. Host arrays only (one device array cannot serve every member's device). The members build the same
+ * boxes with the same code, so they end with the same TLAS; n_tlas_nodes (nullable) receives its node count.
+ * tt_group_scene_update_tlas flags: TT_TRACE_ASYNC. */
+tt_status tt_group_tlas_rebuild(tt_group* g, const float* mesh_aabbs, uint32_t n_mesh, uint32_t flags,
+                                uint32_t* n_tlas_nodes);
+tt_status tt_group_scene_update_tlas(tt_group* g, const tt_cwbvh_node* tlas_nodes, uint32_t n_tlas_nodes,
+                                     const int32_t* tlas_indices, uint32_t n_tlas_indices, uint32_t flags);
 /* One frame: Generate (cam: width / height must be the group's; TT_TRACE_DEVICE_PTRS implied) on every
  * member for its tiles, the primary trace, the gather to rank 0 and, with TT_GROUP_BOUNCE, bounce 1 on
  * every member. hits_out: on the process holding rank 0, a 16-byte-aligned buffer of batch * width * height uint4

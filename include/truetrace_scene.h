@@ -129,6 +129,17 @@ tt_status tt_scene_build_copy(const tt_scene_build* s, tt_cwbvh_node* nodes,
 tt_status tt_scene_build_copy_mesh_aabbs(const tt_scene_build* s, float* out6);
 void tt_scene_build_free(tt_scene_build* s);
 
+/* The builder half of ConstructNewTLAS / CorrectRefit (AssetManager.cs:1350-1356, :1425-1430, :1412) over
+ * caller-supplied world boxes: BVH2Builder's TLAS constructor, BVH8Builder and Aggregate over mesh_aabbs
+ * (n_mesh x {BBMax[3], BBMin[3]}, indexed like _MeshData). It is the code tt_scene_assemble and
+ * tt_scene_assemble_tlas run, so the same boxes give the same bytes. nodes has room for the TLAS region,
+ * 2 * n_mesh nodes, and is written whole: *n_tlas_nodes nodes, then zeros. tlas_indices (n_mesh) receives
+ * TLASBVH8Indices. Pure host code with no state: a host may run it on a worker thread, as the reference
+ * does, and install the result with tt_scene_update_tlas (truetrace_hip.h). TT_ERR_UNSUPPORTED where the
+ * reference's BVH8Builder fails. */
+tt_status tt_tlas_build(const float* mesh_aabbs, uint32_t n_mesh, tt_cwbvh_node* nodes, uint32_t* n_tlas_nodes,
+                        int32_t* tlas_indices);
+
 /* Standalone pieces, exposed for unit tests. */
 /* CommonFunctions.PackOctahedral (CommonVars.cs:816-833) */
 uint32_t tt_pack_octahedral(float x, float y, float z);

@@ -264,8 +264,12 @@ struct tt_ctx {
     tt_ctx* lender = nullptr;  // set on a borrower
     int borrowers = 0;         // on a lender: contexts currently tracing its scene
     // node array sizes: the scene's nodes, and the device array (+ TT_TLAS_SLOTS overlay regions of
-    // tlas_res nodes each behind them, tt_ctx_share_blas)
+    // ovl_stride nodes each behind them, tt_ctx_share_blas); tlas_res: the reach of the uploaded TLAS
     uint32_t n_nodes_scene = 0, n_nodes_dev = 0, tlas_res = 0;
+    // tlas_cap: the scene's own TLAS capacity, the leading nodes no validated BLAS walk reached at upload (an
+    // assembled scene: its tlas_region) -- what a rebuilt TLAS (tt_scene_update_tlas) may grow to. ovl_stride:
+    // the node distance between overlay regions, max(tlas_cap, tlas_res), so a frame slot's rebuilt TLAS fits too.
+    uint32_t tlas_cap = 0, ovl_stride = 0;
     // tt_ctx_share_blas: a borrower with a TLAS of its own (a frame slot's TLAS refit and _MeshData rewrite
     // never wait for, or are seen by, the other slots): its TLAS nodes [0, n_tlas_own) live in overlay region
     // ovl_slot of the lender's node array, at kernel node index tlas_base; TLASBVH8Indices, _MeshData and the

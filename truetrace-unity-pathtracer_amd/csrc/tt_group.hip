@@ -585,6 +585,23 @@ tt_status tt_group_tlas_refit(tt_group* g, uint32_t n_tlas_nodes, const float* m
     return TT_OK;
 }
 
+tt_status tt_group_tlas_rebuild(tt_group* g, const float* mesh_aabbs, uint32_t n_mesh, uint32_t flags,
+                                uint32_t* n_tlas_nodes) {
+    if (!g) return TT_ERR_INVALID_ARG;
+    if (flags & TT_TRACE_DEVICE_PTRS)  // (one device array cannot serve every member's device)
+        return gfail(g, TT_ERR_INVALID_ARG, "tt_group_tlas_rebuild takes host mesh AABBs");
+    for (Member& mb : g->m) G_TT(g, mb.ctx[0], tt_tlas_rebuild(mb.ctx[0], mesh_aabbs, n_mesh, 0, n_tlas_nodes));
+    return TT_OK;
+}
+
+tt_status tt_group_scene_update_tlas(tt_group* g, const tt_cwbvh_node* tlas_nodes, uint32_t n_tlas_nodes,
+                                     const int32_t* tlas_indices, uint32_t n_tlas_indices, uint32_t flags) {
+    if (!g) return TT_ERR_INVALID_ARG;
+    for (Member& mb : g->m)
+        G_TT(g, mb.ctx[0], tt_scene_update_tlas(mb.ctx[0], tlas_nodes, n_tlas_nodes, tlas_indices, n_tlas_indices, flags));
+    return TT_OK;
+}
+
 tt_status tt_group_trace_frame(tt_group* g, const tt_camera* cam, uint32_t* hits_out, uint32_t* info_out,
                                uint32_t flags) {
     if (!g) return TT_ERR_INVALID_ARG;

@@ -7,7 +7,9 @@
 #include <memory>
 
 #include "tt_assemble.h"
+#include "tt_build.h"
 #include "tt_ctx.h"
+#include "tt_tlas_host.h"
 
 namespace {
 
@@ -297,6 +299,43 @@ __global__ void tt_update_mesh_kernel(const tt_mesh_data* __restrict__ src, tt_m
     }
 }
 
+// A whole TLAS installed as one mutation (tt_scene_update_tlas, tt_tlas_rebuild; the launch's shape: tt_tlas::Plan).
+// src_nodes / src_idx are read in place: the pinned staging slot (host memory the GPU reads over the bus) or the
+// device builder's arrays. In 16-B units, 5 per node: units [0, copy_units) are copied to the TLAS region
+// (dst_nodes = nodes + tlas_base, and the strided copy where there is one), units [copy_units, units) cleared, so
+// the region holds what an upload of the host-composed array would. Thread i also stores TLASBVH8Indices[i] and
+// its LeafMesh: the mesh's traversal record as the device holds it (derive_mesh of _MeshData, kept current by
+// tt_update_mesh_kernel) under its new slot. The host validated every index before the launch.
+__global__ void tt_install_tlas_kernel(const uint4* __restrict__ src_nodes, const int32_t* __restrict__ src_idx,
+                                       uint4* __restrict__ dst_nodes, uint8_t* __restrict__ dst_k,
+                                       int32_t* __restrict__ tlas, const MeshGpu* __restrict__ mesh,
+                                       LeafMesh* __restrict__ leaf, uint32_t copy_units, uint32_t units, uint32_t n_idx,
+                                       uint32_t n_mesh) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < units) {
+        const uint4 v = i < copy_units ? src_nodes[i] : make_uint4(0u, 0u, 0u, 0u);
+        dst_nodes[i] = v;
+        if (dst_k) {
+            uint32_t* k = reinterpret_cast<uint32_t*>(dst_k + (size_t)(i / 5u) * TT_NODE_STRIDE + (i % 5u) * 16u);
+            k[0] = v.x;
+            k[1] = v.y;
+            k[2] = v.z;
+            k[3] = v.w;
+        }
+    }
+    if (i < n_idx) {
+        const int32_t m = src_idx[i];
+        tlas[i] = m;
+        if ((uint32_t)m < n_mesh) {
+            LeafMesh l;
+            l.m = mesh[m];
+            l.mesh_id = m;
+            l.pad[0] = l.pad[1] = l.pad[2] = 0;
+            leaf[i] = l;
+        }
+    }
+}
+
 // The host mirror a borrower keeps of its lender's scene: scalars and material records, never the node array
 // or the validation bookkeeping (an overlay borrower adds its own TLAS-side arrays, tt_ctx_share_blas)
 void copy_host_light(SceneHost& d, const SceneHost& s) {
@@ -339,22 +378,29 @@ bool over_4gib(uint64_t n_nodes, uint64_t n_tris) {
 // fills the node and triangle arrays its own way, then scene_commit. Whatever the caller's way, the context ends
 // up the same: same buffers, same sizes, same bookkeeping.
 struct SceneSizes {
-    uint32_t n_nodes = 0, tlas_res = 0, n_nodes_dev = 0;
+    uint32_t n_nodes = 0, tlas_res = 0, n_nodes_dev = 0, tlas_cap = 0, ovl_stride = 0;
 };
 
 // Releases the scene being replaced and allocates the validated scene `h`'s buffers (the cutout / glass records
-// and the leaf records come with scene_commit); the strided node copy starts out zero.
-tt_status scene_alloc(tt_ctx* c, const SceneHost& h, uint32_t n_nodes, uint32_t n_tris, size_t n_tags, SceneSizes& sz) {
+// and the leaf records come with scene_commit); the strided node copy starts out zero. tlas_region: the TLAS
+// region an assembly states (an upload: the node count, so the BLAS walks alone bound the capacity).
+tt_status scene_alloc(tt_ctx* c, const SceneHost& h, uint32_t n_nodes, uint32_t n_tris, size_t n_tags, uint32_t tlas_region,
+                      SceneSizes& sz) {
     SceneDev& d = c->scene;
     d.release_geometry();
     // the TLAS region (every node the TLAS-level walk reaches lies in [0, tlas_res)) and TT_TLAS_SLOTS overlay
-    // regions of that size behind the scene's nodes, for frame slots with TLASes of their own
+    // regions behind the scene's nodes, for frame slots with TLASes of their own; each holds what the scene's own
+    // TLAS region holds (tlas_cap), so a slot's rebuilt TLAS (tt_scene_update_tlas) may outgrow the uploaded one
     sz.n_nodes = n_nodes;
     sz.tlas_res = 0;
     for (uint32_t n : h.tlas_nodes) sz.tlas_res = std::max(sz.tlas_res, n + 1u);
-    if (((uint64_t)n_nodes + (uint64_t)TT_TLAS_SLOTS * sz.tlas_res) * TT_NODE_STRIDE >= (1ull << 32))
-        sz.tlas_res = 0;  // no overlay regions (a node array near the 32-bit limit of the kernels' buffer loads)
-    sz.n_nodes_dev = n_nodes + TT_TLAS_SLOTS * sz.tlas_res;
+    // (a TLAS over n_mesh records never needs more than the reference's 2 * n_mesh nodes)
+    const uint64_t want = std::max<uint64_t>(2ull * h.mesh.size(), sz.tlas_res);
+    sz.tlas_cap = tt_tlas::region_capacity(h.is_blas_node, (uint32_t)std::min<uint64_t>(std::min(n_nodes, tlas_region), want));
+    sz.ovl_stride = std::max(sz.tlas_cap, sz.tlas_res);
+    if (((uint64_t)n_nodes + (uint64_t)TT_TLAS_SLOTS * sz.ovl_stride) * TT_NODE_STRIDE >= (1ull << 32))
+        sz.tlas_res = sz.ovl_stride = 0;  // no overlay regions (a node array near the 32-bit limit of the kernels' buffer loads)
+    sz.n_nodes_dev = n_nodes + TT_TLAS_SLOTS * sz.ovl_stride;
     hipError_t e;
     if ((e = d.nodes.alloc(sz.n_nodes_dev)) != hipSuccess || (e = d.tris_raw.alloc(n_tris)) != hipSuccess ||
         (e = d.tris.alloc(n_tris)) != hipSuccess || (e = d.tlas.alloc(h.tlas.size())) != hipSuccess ||
@@ -390,6 +436,8 @@ tt_status scene_commit(tt_ctx* c, SceneHost&& h, const std::vector<uint32_t>& ta
     c->n_nodes_scene = sz.n_nodes;
     c->n_nodes_dev = sz.n_nodes_dev;
     c->tlas_res = sz.tlas_res;
+    c->tlas_cap = sz.tlas_cap;
+    c->ovl_stride = sz.ovl_stride;
     c->ovl_used = 0;
     c->root_known = true;
     c->any_invisible = any_invisible;
@@ -420,7 +468,7 @@ hipError_t stage_begin(tt_ctx* c, const void* src, size_t bytes, void*& out) {
         if ((e = hipHostMalloc(&pn.p, bytes, hipHostMallocDefault)) != hipSuccess) return e;
         pn.n = bytes;
     }
-    std::memcpy(pn.p, src, bytes);
+    if (src) std::memcpy(pn.p, src, bytes);  // (null: the caller composes the slot's contents itself)
     out = pn.p;
     return hipSuccess;
 }
@@ -470,7 +518,7 @@ tt_status tt_scene_upload(tt_ctx* c, const tt_cwbvh_node* nodes, uint32_t n_node
     for (uint32_t m = 0; m < n_mesh; m++) derive_mesh(md[m], mg[m]);
     SceneSizes sz;
     {
-        const tt_status st = scene_alloc(c, h, n_nodes, n_tris, tags.size(), sz);
+        const tt_status st = scene_alloc(c, h, n_nodes, n_tris, tags.size(), n_nodes, sz);
         if (st != TT_OK) return st;
     }
     TT_HIP(c, hipMemcpy(c->scene.nodes.p, nodes, sizeof(tt_cwbvh_node) * n_nodes, hipMemcpyHostToDevice));
@@ -644,7 +692,7 @@ tt_status tt_scene_assemble_objects(tt_ctx* c, const tt_object* const* objects, 
     for (uint32_t m = 0; m < n_mesh; m++) derive_mesh(md[m], mg[m]);
     SceneSizes sz;
     {
-        const tt_status st = scene_alloc(c, h, n_nodes, n_tris, tags.size(), sz);
+        const tt_status st = scene_alloc(c, h, n_nodes, n_tris, tags.size(), tlas_region, sz);
         if (st != TT_OK) return st;
     }
     hipError_t e;
@@ -757,7 +805,7 @@ tt_status share_begin(tt_ctx* dst, tt_ctx* src) {
     dst->any_invisible = src->any_invisible;
     dst->n_nodes_scene = src->n_nodes_scene;
     dst->n_nodes_dev = src->n_nodes_dev;
-    dst->tlas_res = 0;  // a borrower never lends
+    dst->tlas_res = dst->tlas_cap = dst->ovl_stride = 0;  // a borrower never lends
     dst->ovl = false;
     dst->tlas_base = 0;
     dst->n_tlas_own = 0;
@@ -894,7 +942,7 @@ tt_status tt_ctx_share_blas(tt_ctx* dst, tt_ctx* src, uint32_t n_tlas_nodes) {
     dst->ovl = true;
     dst->ovl_slot = slot;
     dst->n_tlas_own = n_tlas_nodes;
-    dst->tlas_base = src->n_nodes_scene + slot * src->tlas_res;
+    dst->tlas_base = src->n_nodes_scene + slot * src->ovl_stride;
     // device copies: a failure here leaves dst with no scene at all (never a half-linked one)
     auto abort_share = [&](hipError_t err, const char* what) {
         (void)hipStreamSynchronize(dst->stream);
@@ -1216,6 +1264,164 @@ tt_status tt_scene_update_meshdata(tt_ctx* c, uint32_t first, uint32_t count, co
     TT_HIP(c, hipGetLastError());
     TT_HIP(c, stage_end(c));  // (after the kernel: it reads the staging slot)
     TT_HIP(c, sw.end());
+    return TT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// What a TLAS installation on `c` may write: the capacity of its TLAS region and the nodes of it in use now.
+// A scene of its own: the leading nodes no validated BLAS walk reaches (a _MeshData update since the upload may
+// have claimed some); a frame slot: its overlay region, and its own TLAS nodes.
+void tlas_region_of(tt_ctx* c, uint32_t& capacity, uint32_t& used) {
+    if (c->ovl) {
+        std::lock_guard<std::recursive_mutex> lk(c->lender->mu);
+        capacity = c->lender->ovl_stride;
+        used = c->n_tlas_own;
+        return;
+    }
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    capacity = tt_tlas::region_capacity(c->host.is_blas_node, c->tlas_cap);
+    used = tt_tlas::used_nodes(c->host.nodes.data(), capacity);
+}
+
+// The mutation itself, after every check passed: the host state, then tt_install_tlas_kernel on the stream, as a
+// TLAS-side write section (it waits for plain borrowers only, as tt_tlas_refit does). nodes / idx: host copies
+// (the mirror's source); src_nodes / src_idx: what the kernel reads. staged: they are the current pinned slot.
+tt_status install_tlas(tt_ctx* c, const tt_tlas::Plan& p, const tt_cwbvh_node* nodes, const int32_t* idx,
+                       const tt_tlas::Check& k, const void* src_nodes, const void* src_idx, bool staged) {
+    SceneWrite sw(c, false, !c->ovl);  // (an overlay's TLAS is read by nobody else)
+    TT_HIP(c, sw.err);
+    {
+        std::lock_guard<std::recursive_mutex> lk(c->mu);  // node 0 (TT_ROOT_LEAF) is read by launches under it
+        SceneHost& h = c->host;
+        tt_tlas::apply_mirror(p, nodes, idx, k, c->ovl, h.nodes, h.tlas, h.is_tlas_node, h.tlas_nodes);
+        if (c->ovl) c->n_tlas_own = p.n_nodes;
+        // (the reach of the scene's own TLAS only grows: what tt_ctx_share_blas may copy, and what a node rewrite
+        // treats as the TLAS region; 0 stays "no overlay regions")
+        else if (c->tlas_res) c->tlas_res = std::max(c->tlas_res, p.n_nodes);
+        c->root_known = true;  // node 0 is the host's again: the root-leaf step and the leaf kernel follow it
+        c->refit_gen = ~0ull;  // the TLAS refit plan only (the per-mesh BLAS plans follow scene_gen, untouched)
+    }
+    uint32_t slot;
+    TT_HIP(c, ring_open(c, c->timing, slot));
+    hipLaunchKernelGGL(tt_install_tlas_kernel, dim3(p.blocks), dim3(tt_tlas::kInstallBlock), 0, c->stream,
+                       static_cast<const uint4*>(src_nodes), static_cast<const int32_t*>(src_idx),
+                       reinterpret_cast<uint4*>(c->scene.nodes.p + c->tlas_base),
+                       TT_NODE_STRIDE != 80 ? c->scene.nodes_k.p + (size_t)c->tlas_base * TT_NODE_STRIDE : nullptr,
+                       c->scene.tlas.p, c->scene.mesh.p, c->scene.leaf.p, p.copy_units, p.units, p.n_idx,
+                       (uint32_t)c->host.mesh.size());
+    TT_HIP(c, hipGetLastError());
+    if (staged) TT_HIP(c, stage_end(c));  // (after the kernel: it reads the staging slot)
+    TT_HIP(c, ring_close(c, c->timing, slot));
+    TT_HIP(c, sw.end());
+    return TT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+tt_status tt_scene_update_tlas(tt_ctx* c, const tt_cwbvh_node* tlas_nodes, uint32_t n_tlas_nodes,
+                               const int32_t* tlas_indices, uint32_t n_tlas_indices, uint32_t flags) {
+    if (!c) return TT_ERR_INVALID_ARG;
+    TT_REFUSE_DEAD_STREAM(c);
+    TT_REFUSE_BORROWER_TLAS(c);
+    if (!c->has_scene) return fail(c, TT_ERR_NO_SCENE, "no scene uploaded");
+    if (flags & ~(uint32_t)TT_TRACE_ASYNC) return fail(c, TT_ERR_INVALID_ARG, "tt_scene_update_tlas: unknown flag");
+    uint32_t capacity, used;
+    tlas_region_of(c, capacity, used);
+    // the counts first; then the arrays are staged and the staged copy is what gets checked, mirrored and
+    // installed (the caller may reuse, or be racing on, its own arrays)
+    tt_tlas::Check k;
+    if (tt_tlas::check_counts(tlas_nodes, n_tlas_nodes, capacity, tlas_indices, n_tlas_indices,
+                              (uint32_t)c->host.tlas.size(), k) != TT_OK)
+        return fail(c, TT_ERR_INVALID_ARG, "tt_scene_update_tlas: %s", k.why.c_str());
+    TT_HIP(c, hipSetDevice(c->device));
+    const tt_tlas::Plan p = tt_tlas::plan_install(n_tlas_nodes, used, n_tlas_indices);
+    void* pinned = nullptr;
+    TT_HIP(c, stage_begin(c, nullptr, p.stage_bytes, pinned));
+    tt_tlas::fill_stage(p, tlas_nodes, tlas_indices, pinned);
+    const tt_cwbvh_node* nodes = static_cast<const tt_cwbvh_node*>(pinned);
+    const int32_t* idx = reinterpret_cast<const int32_t*>(static_cast<const uint8_t*>(pinned) + p.idx_offset);
+    if (tt_tlas::check_install(nodes, n_tlas_nodes, capacity, idx, n_tlas_indices, (uint32_t)c->host.tlas.size(),
+                               (uint32_t)c->host.mesh.size(), k) != TT_OK)
+        return fail(c, TT_ERR_INVALID_ARG, "tt_scene_update_tlas: %s", k.why.c_str());  // (the slot was not handed on)
+    void* src = nullptr;
+    TT_HIP(c, hipHostGetDevicePointer(&src, pinned, 0));
+    const tt_status st = install_tlas(c, p, nodes, idx, k, src, static_cast<const uint8_t*>(src) + p.idx_offset, true);
+    if (st != TT_OK) return st;
+    if (!(flags & TT_TRACE_ASYNC)) TT_HIP(c, hipStreamSynchronize(c->stream));
+    return TT_OK;
+}
+
+tt_status tt_tlas_rebuild(tt_ctx* c, const float* mesh_aabbs, uint32_t n_mesh, uint32_t flags, uint32_t* n_tlas_nodes) {
+    if (!c) return TT_ERR_INVALID_ARG;
+    TT_REFUSE_DEAD_STREAM(c);
+    TT_REFUSE_BORROWER_TLAS(c);
+    if (!c->has_scene) return fail(c, TT_ERR_NO_SCENE, "no scene uploaded");
+    if (flags & ~(uint32_t)(TT_TRACE_DEVICE_PTRS | TT_TRACE_ASYNC))
+        return fail(c, TT_ERR_INVALID_ARG, "tt_tlas_rebuild: unknown flag");
+    if (!mesh_aabbs || !n_mesh) return fail(c, TT_ERR_INVALID_ARG, "tt_tlas_rebuild: null or empty boxes");
+    if (n_mesh != c->host.mesh.size() || n_mesh != c->host.tlas.size() || n_mesh >= (1u << 29))
+        return fail(c, TT_ERR_INVALID_ARG, "tt_tlas_rebuild: n_mesh %u must equal the scene's _MeshData (%zu) and "
+                                           "TLASBVH8Indices (%zu) counts", n_mesh, c->host.mesh.size(), c->host.tlas.size());
+    uint32_t capacity, used;
+    tlas_region_of(c, capacity, used);
+    TT_HIP(c, hipSetDevice(c->device));
+    const float* d_boxes = mesh_aabbs;
+    if (flags & TT_TRACE_DEVICE_PTRS) {
+        if (!is_device_ptr(mesh_aabbs)) return fail(c, TT_ERR_INVALID_ARG, "TT_TRACE_DEVICE_PTRS set but boxes are not device memory");
+    } else {
+        TT_HIP(c, stage_in(c, c->st_boxes, mesh_aabbs, (size_t)6 * n_mesh, 0, d_boxes));
+    }
+    // ---- build: presort, BVH2 + BVH8 + Aggregate, the forest forms of one tree (they sort <= 16 boxes too)
+    const uint32_t start[2] = {0u, n_mesh};
+    DevBuf<int32_t> pre;
+    TT_HIP(c, pre.alloc(3 * (size_t)n_mesh));
+    uint32_t slot;
+    tt_status s;
+    TT_HIP(c, ring_open(c, c->timing, slot));
+    if ((s = tt_build_presort_forest(c->stream, d_boxes, start, 1, nullptr, pre.p, nullptr)) != TT_OK)
+        return fail(c, s, "tt_tlas_rebuild: %s", tt_build_error());
+    TT_HIP(c, ring_close(c, c->timing, slot));
+    tt_forest_dev F;
+    TT_HIP(c, ring_open(c, c->timing, slot));
+    if ((s = tt_build_blas_forest(c->stream, d_boxes, start, 1, pre.p, F, nullptr)) != TT_OK)
+        return fail(c, s, "tt_tlas_rebuild: %s", tt_build_error());
+    TT_HIP(c, ring_close(c, c->timing, slot));
+    const uint32_t n_nodes = F.node_base[1];
+    if (n_nodes == 0 || n_nodes > capacity || n_nodes > 2ull * n_mesh)
+        return fail(c, TT_ERR_UNSUPPORTED, "tt_tlas_rebuild: the rebuilt TLAS has %u nodes, its region holds %u", n_nodes,
+                    (uint32_t)std::min<uint64_t>(capacity, 2ull * n_mesh));
+    // ---- the small arrays come back for the host-side checks, the mirror and the refit plan
+    std::vector<tt_cwbvh_node> nodes(n_nodes);
+    std::vector<int32_t> idx(n_mesh);
+    TT_HIP(c, hipMemcpyAsync(nodes.data(), F.nodes.p, sizeof(tt_cwbvh_node) * n_nodes, hipMemcpyDeviceToHost, c->stream));
+    TT_HIP(c, hipMemcpyAsync(idx.data(), F.cwbvh_indices.p, sizeof(int32_t) * n_mesh, hipMemcpyDeviceToHost, c->stream));
+    TT_HIP(c, hipStreamSynchronize(c->stream));
+    tt_tlas::Check k;
+    if ((s = tt_tlas::check_install(nodes.data(), n_nodes, capacity, idx.data(), n_mesh, n_mesh, n_mesh, k)) != TT_OK)
+        return fail(c, s, "tt_tlas_rebuild: the built TLAS failed validation: %s", k.why.c_str());
+    // ---- install, sourcing the device arrays
+    const tt_tlas::Plan p = tt_tlas::plan_install(n_nodes, used, n_mesh);
+    if ((s = install_tlas(c, p, nodes.data(), idx.data(), k, F.nodes.p, F.cwbvh_indices.p, false)) != TT_OK) return s;
+    TT_HIP(c, hipStreamSynchronize(c->stream));  // (the builder's arrays are freed on return)
+    if (n_tlas_nodes) *n_tlas_nodes = n_nodes;
+    return TT_OK;
+}
+
+tt_status tt_scene_read_tlas_indices(tt_ctx* c, uint32_t first, uint32_t count, int32_t* out) {
+    if (!c) return TT_ERR_INVALID_ARG;
+    if (!c->has_scene) return fail(c, TT_ERR_NO_SCENE, "no scene uploaded");
+    const size_t n = c->lender && !c->ovl ? c->lender->host.tlas.size() : c->host.tlas.size();
+    if (!out || (uint64_t)first + count > n)
+        return fail(c, TT_ERR_INVALID_ARG, "tt_scene_read_tlas_indices: range out of bounds");
+    TT_HIP(c, hipSetDevice(c->device));
+    SceneRead sr(c);
+    TT_HIP(c, sr.err);
+    TT_HIP(c, hipMemcpyAsync(out, c->scene.tlas.p + first, sizeof(int32_t) * count, hipMemcpyDeviceToHost, c->stream));
+    sr.end();
+    TT_HIP(c, hipStreamSynchronize(c->stream));
     return TT_OK;
 }
 

@@ -1182,6 +1182,18 @@ static AABB transformed_aabb(const AABB& a, const float* l2w) {
     return o;
 }
 
+// The builder half of ConstructNewTLAS / CorrectRefit (AssetManager.cs:1350-1356, :1425-1430): BVH2 over the mesh
+// boxes, then BVH8. False where the reference's BVH8Builder fails, or the tree outgrows the TLAS region (2 * n_mesh).
+static bool build_tlas(const AABB* boxes, uint32_t n_mesh, BVH8Builder& bvh8) {
+    bool ok = false;
+    BVH2Builder bvh2;
+    run_big_stack([&] {
+        bvh2.build(boxes, (int)n_mesh);
+        ok = bvh8.build(bvh2);
+    });
+    return ok && bvh8.BVH8Nodes.size() <= 2ull * n_mesh;
+}
+
 // The TLAS side of AccumulateData / UpdateTLAS / ConstructNewTLAS, from per-object summaries alone: the layout's
 // running sums, _MeshData, MeshAABBs, and the TLAS over them written into s->nodes[0, 2 * n_mesh). Shared by
 // tt_scene_assemble (which then copies the BLASes behind it) and tt_scene_assemble_tlas (which has none to copy).
@@ -1255,14 +1267,8 @@ static tt_status assemble_tlas_side(const tt_object_desc* parents, uint32_t n_pa
     }
 
     // ConstructNewTLAS (:1350-1356, :1411-1412): BVH2 over mesh AABBs, BVH8, Aggregate.
-    bool ok = false;
-    BVH2Builder bvh2;
     BVH8Builder bvh8;
-    run_big_stack([&] {
-        bvh2.build(MeshAABBs.data(), (int)n_mesh);
-        ok = bvh8.build(bvh2);
-    });
-    if (!ok || bvh8.BVH8Nodes.size() > 2ull * n_mesh) return TT_ERR_UNSUPPORTED;
+    if (!build_tlas(MeshAABBs.data(), n_mesh, bvh8)) return TT_ERR_UNSUPPORTED;
     Aggregate(bvh8.BVH8Nodes, s->nodes.data());
     s->tlas_nodes = (uint32_t)bvh8.BVH8Nodes.size();
     s->mesh_aabbs.resize(6 * (size_t)n_mesh);
@@ -1335,6 +1341,24 @@ tt_status tt_scene_assemble_tlas(const tt_object_desc* parents, uint32_t n_paren
     const tt_status st = assemble_tlas_side(parents, n_parents, iparents, n_iparents, instances, n_instances, false, s, node_at, tri_at);
     if (st != TT_OK) { delete s; return st; }
     *out = s;
+    return TT_OK;
+}
+
+tt_status tt_tlas_build(const float* mesh_aabbs, uint32_t n_mesh, tt_cwbvh_node* nodes, uint32_t* n_tlas_nodes,
+                        int32_t* tlas_indices) {
+    if (!mesh_aabbs || !n_mesh || !nodes || !n_tlas_nodes || !tlas_indices || n_mesh > 0x3fffffffu) return TT_ERR_INVALID_ARG;
+    std::vector<AABB> boxes(n_mesh);
+    for (uint32_t i = 0; i < n_mesh; i++) {
+        const float* v = mesh_aabbs + 6 * (size_t)i;
+        boxes[i].BBMax = v3(v[0], v[1], v[2]);
+        boxes[i].BBMin = v3(v[3], v[4], v[5]);
+    }
+    BVH8Builder bvh8;
+    if (!build_tlas(boxes.data(), n_mesh, bvh8)) return TT_ERR_UNSUPPORTED;
+    std::memset(nodes, 0, 2 * (size_t)n_mesh * sizeof(tt_cwbvh_node));
+    Aggregate(bvh8.BVH8Nodes, nodes);
+    *n_tlas_nodes = (uint32_t)bvh8.BVH8Nodes.size();
+    for (uint32_t i = 0; i < n_mesh; i++) tlas_indices[i] = (int32_t)bvh8.cwbvh_indices[i];
     return TT_OK;
 }
 

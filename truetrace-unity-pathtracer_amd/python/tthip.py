@@ -16,7 +16,7 @@ import ctypes as C
 import os
 import weakref
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -218,7 +218,9 @@ HIP_SYMBOLS = ["tt_abi_version", "tt_device_count", "tt_ctx_create", "tt_ctx_des
                "tt_terrain_validate", "tt_trace_heightmap", "tt_trace_heightmap_indirect", "tt_trace_shadow_heightmap",
                "tt_trace_shadow_heightmap_indirect", "tt_object_validate", "tt_object_create", "tt_object_get_info",
                "tt_object_destroy", "tt_scene_layout_objects", "tt_scene_layout_counts", "tt_scene_assemble_objects",
-               "tt_object_build_device", "tt_object_read", "tt_object_leaf_order_device", "tt_objects_build_device"]
+               "tt_object_build_device", "tt_object_read", "tt_object_leaf_order_device", "tt_objects_build_device",
+               "tt_scene_update_tlas", "tt_tlas_rebuild", "tt_scene_read_tlas_indices", "tt_group_tlas_rebuild",
+               "tt_group_scene_update_tlas"]
 SCENE_SYMBOLS = ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_blas_free", "tt_scene_assemble",
                  "tt_scene_build_get_info", "tt_scene_build_copy", "tt_scene_build_free", "tt_pack_octahedral",
                  "tt_bvh2_build", "tt_dotnet_sort_by_key", "tt_synth_cornell", "tt_synth_soup", "tt_synth_sponza",
@@ -227,7 +229,7 @@ SCENE_SYMBOLS = ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_blas_f
                  "tt_blas_build_from_bvh2", "tt_blas_build_from_cwbvh", "tt_blas_prepare",
                  "tt_blas_build_from_cwbvh_prepared", "tt_blas_prep_free", "tt_terrain_trace_host",
                  "tt_terrain_trace_detail_host", "tt_terrain_occluded_host", "tt_terrain_normal_host",
-                 "tt_scene_assemble_tlas", "tt_scene_build_get_totals"]
+                 "tt_scene_assemble_tlas", "tt_scene_build_get_totals", "tt_tlas_build"]
 
 
 def scene_lib():
@@ -254,6 +256,8 @@ def scene_lib():
         L.tt_scene_build_copy.argtypes = [vp, vp, vp, vp, vp]
         L.tt_scene_build_free.argtypes = [vp]
         L.tt_scene_build_copy_mesh_aabbs.argtypes = [vp, vp]
+        L.tt_tlas_build.argtypes = [vp, u32, vp, C.POINTER(u32), vp]
+        L.tt_tlas_build.restype = i32
         L.tt_scene_build_free.restype = None
         L.tt_pack_octahedral.argtypes = [C.c_float, C.c_float, C.c_float]
         L.tt_pack_octahedral.restype = u32
@@ -376,6 +380,12 @@ def hip_lib():
             L.tt_objects_build_device.argtypes = [vp, C.POINTER(MeshInput), u32, C.POINTER(vp), u32, C.POINTER(vp),
                                                   C.POINTER(ObjectBuildInfo), C.POINTER(i32)]
             L.tt_objects_build_device.restype = i32
+        if hasattr(L, "tt_tlas_rebuild"):  # (absent from older libraries)
+            L.tt_scene_update_tlas.argtypes = [vp, vp, u32, vp, u32, u32]
+            L.tt_tlas_rebuild.argtypes = [vp, vp, u32, u32, C.POINTER(u32)]
+            L.tt_scene_read_tlas_indices.argtypes = [vp, u32, u32, vp]
+            for s in ["tt_scene_update_tlas", "tt_tlas_rebuild", "tt_scene_read_tlas_indices"]:
+                getattr(L, s).restype = i32
         L.tt_scene_read_nodes.argtypes = [vp, u32, u32, vp]
         L.tt_scene_read_tris.argtypes = [vp, u32, u32, vp]
         L.tt_blas_refit.argtypes = [vp, C.POINTER(BlasRefitParams), vp, vp, vp]
@@ -929,6 +939,19 @@ class AssetManager:
         return s, objects
 
 
+def tlas_build(mesh_aabbs) -> Tuple[np.ndarray, np.ndarray]:
+    """tt_tlas_build (host): the TLAS over per-mesh world AABBs (n_mesh x {BBMax, BBMin}) as ConstructNewTLAS /
+    CorrectRefit build it. Returns (nodes[:n_tlas_nodes], TLASBVH8Indices); raises TTError(TT_ERR_UNSUPPORTED)
+    where the reference's BVH8Builder fails."""
+    a = np.ascontiguousarray(mesh_aabbs, np.float32).reshape(-1, 6)
+    n = a.shape[0]
+    nodes = np.zeros(2 * n, NODE_DTYPE)
+    idx = np.zeros(n, np.int32)
+    cnt = C.c_uint32()
+    _check(scene_lib().tt_tlas_build(a.ctypes.data, n, nodes.ctypes.data, C.byref(cnt), idx.ctypes.data), "tt_tlas_build")
+    return nodes[: cnt.value].copy(), idx
+
+
 def single_object_scene(mesh: Mesh, local_to_world=None, n_materials: int = 8) -> Scene:
     am = AssetManager()
     am.add_parent(Blas(mesh), local_to_world, np.zeros(n_materials, MAT_DTYPE))
@@ -1426,6 +1449,29 @@ class Engine:
         flags = (TT_TRACE_DEVICE_PTRS if device else 0) | (TT_TRACE_ASYNC if asynchronous else 0)
         self._check(self.L.tt_tlas_refit(self.h, n_tlas_nodes, _ptr(mesh_aabbs), n, flags), "tt_tlas_refit")
 
+    def update_tlas(self, nodes: np.ndarray, tlas_indices: np.ndarray, asynchronous: bool = False):
+        """tt_scene_update_tlas: install a host-built TLAS (tlas_build) -- nodes [0, len(nodes)), the whole
+        TLASBVH8Indices and the leaf records -- as one mutation; the arrays may be reused at once."""
+        nodes = np.ascontiguousarray(nodes, NODE_DTYPE)
+        idx = np.ascontiguousarray(tlas_indices, np.int32)
+        self._check(self.L.tt_scene_update_tlas(self.h, _ptr(nodes), len(nodes), _ptr(idx), len(idx),
+                                                TT_TRACE_ASYNC if asynchronous else 0), "tt_scene_update_tlas")
+
+    def tlas_rebuild(self, mesh_aabbs, device: bool = False) -> int:
+        """tt_tlas_rebuild (AssetManager.CorrectRefit + the swap of RefitTLAS): build a new TLAS over per-mesh
+        world AABBs (n_mesh x {BBMax, BBMin}) on the device and install it. Returns the new n_tlas_nodes."""
+        n = int(mesh_aabbs.shape[0]) if hasattr(mesh_aabbs, "shape") else len(mesh_aabbs) // 6
+        out = C.c_uint32()
+        self._check(self.L.tt_tlas_rebuild(self.h, _ptr(mesh_aabbs), n, TT_TRACE_DEVICE_PTRS if device else 0,
+                                           C.byref(out)), "tt_tlas_rebuild")
+        return int(out.value)
+
+    def scene_tlas_indices(self, first: int, count: int) -> np.ndarray:
+        """Reads TLASBVH8Indices [first, first+count) back from HBM (the counterpart of scene_nodes)."""
+        out = np.zeros(count, np.int32)
+        self._check(self.L.tt_scene_read_tlas_indices(self.h, first, count, _ptr(out)), "tt_scene_read_tlas_indices")
+        return out
+
     def blas_refit(self, mesh_index: int, vertices, indices, leaf_of_triangle, transform=None,
                    device: bool = False, asynchronous: bool = False):
         """tt_blas_refit (ParentObject.RefitMesh): re-derive the mesh's triangles from `vertices`
@@ -1660,6 +1706,11 @@ def _bind_group(L):
         if hasattr(L, "tt_group_scene_upload_terrains"):  # (absent from older variant libraries)
             L.tt_group_scene_upload_terrains.argtypes = [vp, vp, u32, vp, u32, u32]
             L.tt_group_scene_upload_terrains.restype = i32
+        if hasattr(L, "tt_group_tlas_rebuild"):  # (absent from older libraries)
+            L.tt_group_tlas_rebuild.argtypes = [vp, vp, u32, u32, C.POINTER(u32)]
+            L.tt_group_tlas_rebuild.restype = i32
+            L.tt_group_scene_update_tlas.argtypes = [vp, vp, u32, vp, u32, u32]
+            L.tt_group_scene_update_tlas.restype = i32
         L.tt_group_sync.argtypes = [vp]
         L.tt_group_frame_rays.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(vp)]
         L.tt_group_tile_pixels.argtypes = [u32, u32, u32, u32, u32, vp, u32, C.POINTER(u32)]
@@ -1781,6 +1832,21 @@ class Group:
         a = np.ascontiguousarray(mesh_aabbs, np.float32)
         self._check(self.L.tt_group_tlas_refit(self.h, n_tlas_nodes, a.ctypes.data, a.shape[0],
                                                TT_TRACE_ASYNC if asynchronous else 0), "tt_group_tlas_refit")
+
+    def tlas_rebuild(self, mesh_aabbs: np.ndarray) -> int:
+        """tt_group_tlas_rebuild: every member rebuilds its TLAS over the (host) boxes; the new n_tlas_nodes."""
+        a = np.ascontiguousarray(mesh_aabbs, np.float32)
+        out = C.c_uint32()
+        self._check(self.L.tt_group_tlas_rebuild(self.h, a.ctypes.data, a.shape[0], 0, C.byref(out)),
+                    "tt_group_tlas_rebuild")
+        return int(out.value)
+
+    def update_tlas(self, nodes: np.ndarray, tlas_indices: np.ndarray, asynchronous: bool = False):
+        nodes = np.ascontiguousarray(nodes, NODE_DTYPE)
+        idx = np.ascontiguousarray(tlas_indices, np.int32)
+        self._check(self.L.tt_group_scene_update_tlas(self.h, _ptr(nodes), len(nodes), _ptr(idx), len(idx),
+                                                      TT_TRACE_ASYNC if asynchronous else 0),
+                    "tt_group_scene_update_tlas")
 
     def frame_rays(self, m: int = 0):
         """(n_primary, n_bounce, device pointer of the ray buffer) of member m's latest frame."""
