@@ -7,6 +7,10 @@ y = -1.6, so the hill tops poke through the box floor at y = -1); terrain 1 (4 x
 terrain 0 in x in [2, 4] and continues to x = 6, beyond terrain 0's footprint. The 64 x 48 atlas holds terrain 0
 on the 33 x 33 rectangle at texel (4, 3) and terrain 1 on the 17 x 17 rectangle at texel (44, 20); terrain 1's
 left half is a plateau (constant height 0.5), which is where a ray skimming the surface spends all 2,000 steps.
+
+The same scene, with the head of the ray sets, is compared with a float64 heightmap surface instead of the host
+reference in tests/test_terrain_geometry_host.py and tests/test_gpu_terrain_geometry.py (tests/terrain_geometry.py,
+tests/terrain_geometry_cases.py).
 """
 import functools
 
