@@ -77,6 +77,31 @@ namespace TrueTrace.Hip
         public uint flags;
     }
 
+    /// tt_blas_refit_part: one renderer of a skinned group (one Construct dispatch of RefitMesh's loop).
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct TTBlasRefitPart
+    {
+        public float* vertices;    // nVertices x vertexStride floats; device memory with TTTraceFlags.DevicePtrs
+        public uint nVertices;
+        public uint vertexStride;
+        public int* indices;       // 3 per triangle, local to this renderer's vertex buffer
+        public uint nTris;
+        public uint firstTri;      // VertOffset
+        public fixed float transform[16];
+    }
+
+    /// tt_blas_refit_item: one deforming mesh, its renderers, and (optionally) the matrix for its world box.
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct TTBlasRefitItem
+    {
+        public uint meshIndex;
+        public uint nTris;
+        public int* leafOfTriangle;
+        public TTBlasRefitPart* parts;
+        public uint nParts;
+        public float* localToWorld;  // null, or 16 floats column-major (host memory)
+    }
+
     /// Generate's camera (RayGenKernels.compute:40-57): Unity's cameraToWorldMatrix and projectionMatrix.inverse,
     /// column-major (the memory order of UnityEngine.Matrix4x4).
     [StructLayout(LayoutKind.Sequential)]
@@ -240,6 +265,11 @@ namespace TrueTrace.Hip
         // ParentObject.RefitMesh: vertex buffer (floats), sharedMesh.triangles, CWBVHIndicesBufferInverted.
         [DllImport(Lib)] public static extern unsafe TTStatus tt_blas_refit(IntPtr ctx, ref TTBlasRefitParams p, float* vertices,
             int* indices, int* leafOfTriangle);
+        // RefitMesh for a frame's deforming meshes, renderer by renderer, in two launches; boundsOut / meshAabbs may be null
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_blas_refit_many(IntPtr ctx, TTBlasRefitItem* items, uint nItems,
+            uint flags, float* boundsOut, float* meshAabbs);
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_blas_refit_items_validate(TTBlasRefitItem* items, uint nItems,
+            void* meshData, uint nMesh, uint nSceneTris, uint flags, byte* why, uint whyLen);
         [DllImport(Lib)] public static extern TTStatus tt_sync(IntPtr ctx);
         [DllImport(Lib)] public static extern unsafe TTStatus tt_scene_read_tris(IntPtr ctx, uint first, uint count, void* tris);
         [DllImport(Lib)] public static extern TTStatus tt_scene_bytes(IntPtr ctx, out ulong bytes);
@@ -745,6 +775,15 @@ namespace TrueTrace.Hip
             for (int i = 0; i < 16; i++) p.transform[i] = transform.m[i];
             fixed (float* v = vertices) fixed (int* t = triangles) fixed (int* l = leafOfTriangle)
                 Check(Native.tt_blas_refit(m_ctx, ref p, v, t, l));
+        }
+
+        /// tt_blas_refit_many: the frame's deforming meshes in one call. The caller fills the items (and pins or
+        /// owns the arrays they point to); the descriptors may be reused as soon as this returns.
+        public unsafe void RefitMeshes(TTBlasRefitItem[] items, TTTraceFlags flags = 0, float* boundsOut = null,
+                                       float* meshAabbs = null)
+        {
+            fixed (TTBlasRefitItem* p = items)
+                Check(Native.tt_blas_refit_many(m_ctx, p, (uint)items.Length, (uint)flags, boundsOut, meshAabbs));
         }
 
         /// tt_object_create: one ParentObject's BLAS (nodes and AggTriangles with BLAS-local indices) resident on

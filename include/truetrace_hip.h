@@ -509,6 +509,66 @@ typedef struct tt_blas_refit_params {
 tt_status tt_blas_refit(tt_ctx* ctx, const tt_blas_refit_params* p, const float* vertices, const int32_t* indices,
                         const int32_t* leaf_of_triangle);
 
+/* A frame's deforming meshes in one call: ParentObject.RefitMesh (ParentObject.cs:857-877) for any number of
+ * meshes, each given as the renderers of its skinned group. The reference runs Construct once per renderer --
+ * its own vertex buffer and Stride, its own Transform (worldToLocal * TRS(rootBone), :865), its own VertOffset
+ * into CWBVHIndices (BVHRefitter.compute:88) -- and only then one refit pass over the BLAS. Here a renderer is a
+ * tt_blas_refit_part, a mesh a tt_blas_refit_item, and the whole list costs two launches: one Construct over
+ * every part of every item, one refit over every item's leaf NodePairs.
+ *   Every triangle t of a part goes through Construct exactly as in tt_blas_refit (same pinned arithmetic, the
+ * (i0, i2, i1) order, the 1e-6 padding) and lands at leaf_of_triangle[first_tri + t] of its item; an
+ * out-of-range vertex read gives zeros, a leaf position outside [0, item.n_tris) drops the write. Then every
+ * item's BLAS is refitted as tt_blas_refit does it. The device bytes afterwards (nodes, AggTris, traversal
+ * records, the kernel-layout node copy) are those of the same refits made one mesh at a time; an item with one
+ * part gives tt_blas_refit's bytes.
+ *   The ranges [first_tri, first_tri + n_tris) of an item's parts must cover [0, item.n_tris) exactly once, in
+ * any order (the reference constructs every renderer; a gap would keep boxes of an earlier frame).
+ *   bounds_out (nullable, n_items x {BBMax[3], BBMin[3]}): each item's object-space root box as the refit's root
+ * NodePair computed it. mesh_aabbs (nullable, the n_mesh x 6 array tt_tlas_refit takes): for every item with
+ * local_to_world, slot mesh_index receives the box over the eight corners of that root box, each corner through
+ * fmaf(m2, z, fmaf(m1, y, m0 * x)) + m3, max / min as maxNum / minNum; no other slot is touched (other records
+ * instancing the same BLAS are the caller's). The thread that completes an item's root writes both: no further
+ * launch, no read-back, so refit -> tt_tlas_refit -> trace chains on the stream with no host wait.
+ *   flags: TT_TRACE_DEVICE_PTRS -- every vertices / indices / leaf_of_triangle array, bounds_out and mesh_aabbs
+ * are device memory; the item, part and matrix descriptors are always host memory and are copied to pinned
+ * staging before the call returns. TT_TRACE_ASYNC is honoured only with device pointers. Without
+ * TT_TRACE_DEVICE_PTRS every array is staged, indices and leaf positions are range-checked on the host, and the
+ * call synchronizes.
+ *   Ordering and sharing are tt_blas_refit's (one BLAS-side mutation for the batch, refused on borrowers, one
+ * tt_timing_read entry). The composed plan and its device arrays are cached for (scene, ordered list of
+ * (mesh_index, n_tris, the record's NodeOffset)): a frame with the same list as the last allocates nothing and
+ * does not synchronize.
+ *   Refused with TT_ERR_INVALID_ARG (reason in tt_last_error) before anything is enqueued: n_items == 0, a null
+ * array, an empty item or part, vertex_stride < 6, a mesh index out of range or given twice, two items whose
+ * records share a NodeOffset (one BLAS: their arrival counters would race), parts that overlap or leave a gap,
+ * TriOffset + n_tris beyond the scene, the device flag with a host pointer, more than TT_BLAS_REFIT_MANY_MAX_TRIS
+ * triangles in all (leaf ranges are 24 * position + count in an int32); TT_ERR_UNSUPPORTED for a BLAS whose
+ * root is not its first node. tt_blas_refit_items_validate is the host-only half of these checks (everything
+ * that needs neither node data nor a device): `why` receives the first violation. */
+#define TT_BLAS_REFIT_MANY_MAX_TRIS (1u << 26)
+typedef struct tt_blas_refit_part {  /* one renderer of the group: one Construct dispatch of the reference */
+    const float* vertices;           /* n_vertices x vertex_stride floats, position at +0, normal at +3   */
+    uint32_t n_vertices;
+    uint32_t vertex_stride;          /* floats per vertex, >= 6                                            */
+    const int32_t* indices;          /* 3 per triangle, local to this part's vertex buffer                 */
+    uint32_t n_tris;
+    uint32_t first_tri;              /* VertOffset: triangle t is source triangle first_tri + t of the mesh */
+    float transform[16];             /* column-major, as tt_blas_refit_params.transform                    */
+} tt_blas_refit_part;
+typedef struct tt_blas_refit_item {
+    uint32_t mesh_index;             /* the _MeshData record                                               */
+    uint32_t n_tris;                 /* its BLAS's triangle count                                          */
+    const int32_t* leaf_of_triangle; /* n_tris, CWBVHIndicesBufferInverted                                 */
+    const tt_blas_refit_part* parts;
+    uint32_t n_parts;
+    const float* local_to_world;     /* nullable, 16 floats column-major: see mesh_aabbs                   */
+} tt_blas_refit_item;
+tt_status tt_blas_refit_many(tt_ctx* ctx, const tt_blas_refit_item* items, uint32_t n_items, uint32_t flags,
+                             float* bounds_out, float* mesh_aabbs);
+tt_status tt_blas_refit_items_validate(const tt_blas_refit_item* items, uint32_t n_items, const tt_mesh_data* meshdata,
+                                       uint32_t n_mesh, uint32_t n_scene_tris, uint32_t flags, char* why,
+                                       uint32_t why_len);
+
 /* BLAS builder, BVH2 stage, on the GPU (row f4's builder half): BVH2Builder (BVH2Builder.cs:9-217)
  * restated level by level -- segmented AABB.Extend scans, the full-sweep SAH with the reference's
  * tie rules, stable partitions -- with outputs identical to the sequential C# recursion and to
@@ -735,9 +795,9 @@ tt_status tt_trace_chunk_costs(tt_ctx* ctx, int32_t bounce, uint32_t* costs, uin
 /* Per-call GPU durations (HIP events on the context stream, in issue order) since the last
  * tt_timing_reset (ring of 256 entries). One entry per call of tt_trace_closest and
  * tt_trace_shadow (the trace kernel alone), tt_generate_primary (the generate kernel),
- * tt_enqueue_diffuse_bounce (counter reset + enqueue kernel), tt_tlas_refit and tt_blas_refit
- * (the whole device-side refit). Host<->device staging copies are never inside an entry.
- * Synchronizes. */
+ * tt_enqueue_diffuse_bounce (counter reset + enqueue kernel), tt_tlas_refit, tt_blas_refit and
+ * tt_blas_refit_many (the whole device-side refit; one entry for the whole list).
+ * Host<->device staging copies are never inside an entry. Synchronizes. */
 tt_status tt_timing_reset(tt_ctx* ctx);
 tt_status tt_timing_read(tt_ctx* ctx, float* ms, uint32_t max, uint32_t* n);
 /* Per-call timing on (default) or off. Off: asynchronous calls (TT_TRACE_ASYNC, device-resident counts)

@@ -298,6 +298,7 @@ tt_status tt_ctx_destroy(tt_ctx* c) {
     if (c->ev_read) (void)hipEventDestroy(c->ev_read);
     tt_refit_free(c->refit);
     for (auto& kv : c->blas_refit) tt_refit_free(kv.second.dev);
+    tt_refit_free(c->refit_many.dev);
     if (c->ctl) (void)hipFree(c->ctl);
     for (uint32_t i = 0; i < TT_RING; i++) {
         if (c->ring0[i]) (void)hipEventDestroy(c->ring0[i]);

@@ -223,6 +223,27 @@ struct tt_ctx {
     };
 
     std::map<uint32_t, BlasRefit> blas_refit;
+    // tt_blas_refit_many: the host plan of each mesh it has seen (a changed list only re-composes), and the
+    // composed forest of the last list with its device arrays -- valid for (scene generation, the ordered list of
+    // (mesh_index, n_tris, NodeOffset)), so a frame with the same list allocates nothing and builds no plan
+    struct BlasPlanHost {
+        RefitPlan plan;
+        uint32_t n_nodes = 0;
+        uint64_t gen = ~0ull;
+        uint32_t node_base = ~0u;
+    };
+    std::map<uint32_t, BlasPlanHost> many_plans;
+    struct BlasRefitMany {
+        uint64_t gen = ~0ull;
+        std::vector<uint32_t> key;       // mesh_index, n_tris, NodeOffset per item, in list order
+        std::vector<uint32_t> box_base;  // per item: its first box in the pool
+        RefitDev dev;
+        DevBuf<float> boxes;             // the pool: every item's triangle boxes
+        DevBuf<uint8_t> desc;            // the call's part / item / block descriptors
+        DevBuf<float> bounds;            // bounds_out of a host-pointer call
+        std::vector<std::pair<uint32_t, uint32_t>> node_ranges;  // [first, end) of the items' BLAS nodes, adjacent ones merged
+    };
+    BlasRefitMany refit_many;
     DevBuf<float> st_vtx;
     DevBuf<int32_t> st_idx, st_leaf;
     // host-pointer staging

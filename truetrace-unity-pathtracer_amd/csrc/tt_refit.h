@@ -52,4 +52,38 @@ struct BlasConstructArgs {
 hipError_t tt_blas_construct(const BlasConstructArgs& a, hipStream_t st);
 void tt_refit_free(RefitDev& d);
 
+// tt_blas_refit_many: Construct over all parts of all items in one launch, then one refit launch over the
+// composed forest of the items' plans. The three descriptor arrays are rewritten every call (pointers and
+// matrices are the frame's) and read by the kernels from one device buffer.
+struct RefitManyPart {        // one renderer: block-uniform in blas_construct_many
+    const float* vertices;
+    const int32_t* indices;
+    const int32_t* leaf_of;   // the item's leaf_of_triangle + first_tri
+    float* boxes;             // the item's boxes in the pool
+    tt_cuda_triangle* tris88; // AggTris + the item's TriOffset
+    TriPos* tripos;           // traversal layout + the item's TriOffset
+    uint32_t n_tris, n_vertices, vertex_stride;
+    uint32_t leaf_bound;      // the item's triangle count
+    float m[16];
+};
+struct RefitManyBlock {       // block b of the Construct launch: triangles [first, first + 256) of part `part`
+    uint32_t part, first;
+};
+struct RefitManyItem {        // what the thread completing the item's root needs
+    float l2w[16];
+    uint32_t mesh_index, has_l2w, pad[2];
+};
+static_assert(sizeof(RefitManyPart) == 128 && sizeof(RefitManyItem) == 80 && sizeof(RefitManyBlock) == 8, "descriptor layout");
+struct RefitForestItem {
+    const RefitPlan* plan;
+    uint32_t node_base;  // the BLAS's first node in the scene's node array
+    uint32_t n_nodes;    // nodes the plan covers
+    uint32_t box_base;   // the item's first box in the pool (in boxes)
+};
+hipError_t tt_refit_prepare_forest(const std::vector<RefitForestItem>& items, RefitDev& d);
+// items: the device array, one per tree; or null and `one` (host): a forest of one tree, its item in the kernel arguments
+hipError_t tt_refit_run_forest(RefitDev& d, const float* boxes, tt_cwbvh_node* nodes, const RefitManyItem* items,
+                               const RefitManyItem* one, float* bounds_out, float* mesh_aabbs, hipStream_t st);
+hipError_t tt_blas_construct_many(const RefitManyPart* parts, const RefitManyBlock* blocks, uint32_t n_blocks, hipStream_t st);
+
 #endif  // TT_REFIT_H

@@ -175,17 +175,66 @@ struct RefitTreeArgs {
     tt_cwbvh_node* nodes;
 };
 
-__global__ void refit_tree(RefitTreeArgs t) {
+// The forest form (tt_blas_refit_many): the composed plans of several BLASes in one set of arrays, pair ids
+// offset per item, node_of scene-global, leaf ranges offset by the item's place in the box pool. A tree's root
+// is the pair whose parent entry is -1 - item; the thread that completes it also writes the item's bounds.
+struct RefitForestArgs {
+    const RefitManyItem* items;  // null: a forest of one tree, its item in `one`
+    RefitManyItem one;
+    float* bounds_out;  // nullable: n_items x {BBMax, BBMin}, the root pairs' boxes
+    float* mesh_aabbs;  // nullable: slot mesh_index of every item with a local_to_world
+};
+
+__device__ __forceinline__ float M(const float* m, int r, int c) { return m[c * 4 + r]; }
+__device__ __forceinline__ float3 xform_point(const float* m, float3 p) {
+    return make_float3(__builtin_fmaf(M(m, 0, 2), p.z, __builtin_fmaf(M(m, 0, 1), p.y, M(m, 0, 0) * p.x)) + M(m, 0, 3),
+                       __builtin_fmaf(M(m, 1, 2), p.z, __builtin_fmaf(M(m, 1, 1), p.y, M(m, 1, 0) * p.x)) + M(m, 1, 3),
+                       __builtin_fmaf(M(m, 2, 2), p.z, __builtin_fmaf(M(m, 2, 1), p.y, M(m, 2, 0) * p.x)) + M(m, 2, 3));
+}
+
+__device__ __forceinline__ void forest_root(const RefitForestArgs& f, uint32_t item, const float box[6]) {
+    if (f.bounds_out) {
+        float* o = f.bounds_out + 6 * (size_t)item;
+        for (int k = 0; k < 6; k++) o[k] = box[k];
+    }
+    const RefitManyItem& it = f.items ? f.items[item] : f.one;
+    if (!f.mesh_aabbs || !it.has_l2w) return;
+    float3 mx, mn;
+    for (int c = 0; c < 8; c++) {  // the eight corners of {BBMax, BBMin}
+        const float3 w = xform_point(it.l2w, make_float3(box[c & 1 ? 0 : 3], box[c & 2 ? 1 : 4], box[c & 4 ? 2 : 5]));
+        mx = c ? make_float3(fmaxf(mx.x, w.x), fmaxf(mx.y, w.y), fmaxf(mx.z, w.z)) : w;
+        mn = c ? make_float3(fminf(mn.x, w.x), fminf(mn.y, w.y), fminf(mn.z, w.z)) : w;
+    }
+    float* o = f.mesh_aabbs + 6 * (size_t)it.mesh_index;
+    o[0] = mx.x;
+    o[1] = mx.y;
+    o[2] = mx.z;
+    o[3] = mn.x;
+    o[4] = mn.y;
+    o[5] = mn.z;
+}
+
+// One tree (kForest = false: the TLAS, one BLAS) ends at pair 0; a forest at each item's root pair.
+template <bool kForest>
+__device__ __forceinline__ void refit_climb(const RefitTreeArgs& t, const RefitForestArgs& f) {
     const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
     if (s >= t.n_starts) return;
     const __amdgpu_buffer_rsrc_t bb = __builtin_amdgcn_make_buffer_rsrc(t.bb, 0, (int)(t.n_pairs * 32u), 0x00020000);
     int32_t id = t.starts[s];
     float box[6];
     leaf_union(id, t.fwd, t.box_idx, t.boxes, box);
-    while (id != 0) {  // the root pair completes the tree
+    while (kForest || id != 0) {  // the root pair completes the tree
+        int32_t p;
+        if (kForest) {
+            p = t.parent[id];
+            if (p < 0) {
+                forest_root(f, (uint32_t)(-p - 1), box);
+                return;
+            }
+        }
         st_box(bb, id, box);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the box has left this CU before the arrival
-        const int32_t p = t.parent[id];
+        if (!kForest) p = t.parent[id];
         const uint32_t prev = __hip_atomic_fetch_add(t.arrive + p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (prev != 7u) return;  // not the last of the parent's 8 slots
         // the other 7 boxes were stored sc1 by threads of other workgroups (often other CUs / XCDs):
@@ -200,20 +249,28 @@ __global__ void refit_tree(RefitTreeArgs t) {
     }
 }
 
+__global__ void refit_tree(RefitTreeArgs t) { refit_climb<false>(t, RefitForestArgs{}); }
+__global__ void refit_forest(RefitTreeArgs t, RefitForestArgs f) { refit_climb<true>(t, f); }
+
 // ------------------------------------------------------------------ Construct (BLAS refit)
 // The reference leaves normalize / round / the mul association to DXC; pinned here and in the
 // oracle: mul rows as fmaf(m2, z, fmaf(m1, y, m0 * x)) (+ m3), normalize(v) = v * (1 / sqrt(dot))
 // with dot = fmaf(z, z, fmaf(y, y, x * x)), round = round-half-to-even, no other contraction.
-__device__ __forceinline__ float3 ld_vec3(const BlasConstructArgs& a, int32_t idx, uint32_t off) {
+// One part of a mesh (a whole mesh for tt_blas_refit): what Construct reads and where it writes.
+struct ConstructPart {
+    const float* vertices;
+    const int32_t *indices, *leaf_of;
+    uint32_t n_vertices, vertex_stride;
+    uint32_t leaf_bound;  // leaf positions are valid in [0, leaf_bound): the mesh's triangle count
+    const float* m;
+    float* boxes;
+    tt_cuda_triangle* tris88;
+    TriPos* tripos;
+};
+__device__ __forceinline__ float3 ld_vec3(const ConstructPart& a, int32_t idx, uint32_t off) {
     if (idx < 0 || (uint32_t)idx >= a.n_vertices) return make_float3(0.0f, 0.0f, 0.0f);  // D3D: OOB reads 0
     const float* v = a.vertices + (size_t)idx * a.vertex_stride + off;
     return make_float3(v[0], v[1], v[2]);
-}
-__device__ __forceinline__ float M(const float* m, int r, int c) { return m[c * 4 + r]; }
-__device__ __forceinline__ float3 xform_point(const float* m, float3 p) {
-    return make_float3(__builtin_fmaf(M(m, 0, 2), p.z, __builtin_fmaf(M(m, 0, 1), p.y, M(m, 0, 0) * p.x)) + M(m, 0, 3),
-                       __builtin_fmaf(M(m, 1, 2), p.z, __builtin_fmaf(M(m, 1, 1), p.y, M(m, 1, 0) * p.x)) + M(m, 1, 3),
-                       __builtin_fmaf(M(m, 2, 2), p.z, __builtin_fmaf(M(m, 2, 1), p.y, M(m, 2, 0) * p.x)) + M(m, 2, 3));
 }
 __device__ __forceinline__ float3 xform_normal(const float* m, float3 n) {
     const float3 v = make_float3(__builtin_fmaf(M(m, 0, 2), n.z, __builtin_fmaf(M(m, 0, 1), n.y, M(m, 0, 0) * n.x)),
@@ -236,9 +293,8 @@ __device__ __forceinline__ uint32_t octahedral_32(float3 n) {
     return dx | (dy << 16);
 }
 
-__global__ void blas_construct(BlasConstructArgs a) {
-    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-    if (t >= a.n_tris) return;
+// Construct of the part's triangle t (t < the part's triangle count).
+__device__ __forceinline__ void construct_tri(const ConstructPart& a, uint32_t t) {
     const int32_t i0 = a.indices[3 * t], i1 = a.indices[3 * t + 1], i2 = a.indices[3 * t + 2];
     // vidx = Load3(...).xzy: p from i0, p2 from i2, p3 from i1
     const float3 p = xform_point(a.m, ld_vec3(a, i0, 0)), p2 = xform_point(a.m, ld_vec3(a, i2, 0)),
@@ -246,7 +302,7 @@ __global__ void blas_construct(BlasConstructArgs a) {
     const float3 n1 = xform_normal(a.m, ld_vec3(a, i0, 3)), n2 = xform_normal(a.m, ld_vec3(a, i2, 3)),
                  n3 = xform_normal(a.m, ld_vec3(a, i1, 3));
     const int32_t leaf = a.leaf_of[t];
-    if (leaf < 0 || (uint32_t)leaf >= a.n_tris) return;  // D3D drops out-of-range writes
+    if (leaf < 0 || (uint32_t)leaf >= a.leaf_bound) return;  // D3D drops out-of-range writes
     float mx[3] = {fmaxf(fmaxf(p.x, p2.x), p3.x), fmaxf(fmaxf(p.y, p2.y), p3.y), fmaxf(fmaxf(p.z, p2.z), p3.z)};
     float mn[3] = {fminf(fminf(p.x, p2.x), p3.x), fminf(fminf(p.y, p2.y), p3.y), fminf(fminf(p.z, p2.z), p3.z)};
     for (int k = 0; k < 3; k++)
@@ -285,6 +341,24 @@ __global__ void blas_construct(BlasConstructArgs a) {
     q.e2x = e2.x;
     q.e2y = e2.y;
     q.e2z = e2.z;
+}
+
+__global__ void blas_construct(BlasConstructArgs a) {
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= a.n_tris) return;
+    construct_tri(ConstructPart{a.vertices, a.indices, a.leaf_of, a.n_vertices, a.vertex_stride, a.n_tris, a.m, a.boxes,
+                                a.tris88, a.tripos}, t);
+}
+
+// All parts of all items in one launch (tt_blas_refit_many). No block straddles two parts: block b serves the
+// triangles [first, first + 256) of part `part` (the block table), so the part's descriptor is block-uniform.
+__global__ void blas_construct_many(const RefitManyPart* __restrict__ parts, const RefitManyBlock* __restrict__ blocks) {
+    const RefitManyBlock b = blocks[blockIdx.x];
+    const RefitManyPart& a = parts[b.part];
+    const uint32_t t = b.first + threadIdx.x;
+    if (t >= a.n_tris) return;
+    construct_tri(ConstructPart{a.vertices, a.indices, a.leaf_of, a.n_vertices, a.vertex_stride, a.leaf_bound, a.m, a.boxes,
+                                a.tris88, a.tripos}, t);
 }
 
 inline uint32_t grid_of(uint32_t n) { return (n + kBlock - 1) / kBlock; }
@@ -398,6 +472,55 @@ hipError_t tt_refit_run(RefitDev& d, const float* boxes, const int32_t* box_inde
     if (!d.n_starts) return hipSuccess;
     RefitTreeArgs t{d.starts, d.n_starts, d.fwd, d.parent, d.node_of, d.arrive, d.bb, d.n_pairs, boxes, box_index, nodes};
     hipLaunchKernelGGL(refit_tree, dim3(grid_of(d.n_starts)), dim3(kBlock), 0, st, t);
+    return hipGetLastError();
+}
+
+// The plans of several BLASes composed into one forest (the forest form above). Counters zeroed once.
+hipError_t tt_refit_prepare_forest(const std::vector<RefitForestItem>& items, RefitDev& d) {
+    tt_refit_free(d);
+    std::vector<int32_t> starts, fwd, parent, node_of;
+    size_t N = 0;
+    for (const RefitForestItem& it : items) N += it.plan->pair_bvh.size();
+    fwd.reserve(N * 8);
+    parent.reserve(N);
+    node_of.assign(N, -1);
+    int32_t base = 0;
+    for (size_t i = 0; i < items.size(); i++) {
+        const RefitPlan& R = *items[i].plan;
+        const int32_t n = (int32_t)R.pair_bvh.size(), box24 = (int32_t)items[i].box_base * 24;
+        for (int32_t k = 0; k < n; k++) {
+            if (R.leaf[k]) starts.push_back(base + k);
+            parent.push_back(k == 0 ? -1 - (int32_t)i : base + R.parent[k]);
+        }
+        for (int32_t e : R.fwd) fwd.push_back(e < 0 ? e - base : e > 0 ? e + box24 : 0);
+        for (uint32_t b = 0; b < items[i].n_nodes; b++)
+            if (b == 0 || R.to_bvh[b] != 0) node_of[(size_t)base + R.to_bvh[b]] = (int32_t)(items[i].node_base + b);
+        base += n;
+    }
+    d.n_pairs = (uint32_t)N;
+    d.n_nodes = 0;
+    d.n_starts = (uint32_t)starts.size();
+    hipError_t e;
+    if ((e = up(&d.starts, starts)) != hipSuccess || (e = up(&d.fwd, fwd)) != hipSuccess ||
+        (e = up(&d.parent, parent)) != hipSuccess || (e = up(&d.node_of, node_of)) != hipSuccess)
+        return e;
+    if ((e = hipMalloc(reinterpret_cast<void**>(&d.arrive), sizeof(uint32_t) * N)) != hipSuccess) return e;
+    if ((e = hipMemset(d.arrive, 0, sizeof(uint32_t) * N)) != hipSuccess) return e;
+    return hipMalloc(reinterpret_cast<void**>(&d.bb), 8 * sizeof(float) * N);
+}
+
+hipError_t tt_refit_run_forest(RefitDev& d, const float* boxes, tt_cwbvh_node* nodes, const RefitManyItem* items,
+                               const RefitManyItem* one, float* bounds_out, float* mesh_aabbs, hipStream_t st) {
+    if (!d.n_starts) return hipSuccess;
+    RefitTreeArgs t{d.starts, d.n_starts, d.fwd, d.parent, d.node_of, d.arrive, d.bb, d.n_pairs, boxes, nullptr, nodes};
+    hipLaunchKernelGGL(refit_forest, dim3(grid_of(d.n_starts)), dim3(kBlock), 0, st, t,
+                       RefitForestArgs{items, one ? *one : RefitManyItem{}, bounds_out, mesh_aabbs});
+    return hipGetLastError();
+}
+
+hipError_t tt_blas_construct_many(const RefitManyPart* parts, const RefitManyBlock* blocks, uint32_t n_blocks, hipStream_t st) {
+    if (!n_blocks) return hipSuccess;
+    hipLaunchKernelGGL(blas_construct_many, dim3(n_blocks), dim3(kBlock), 0, st, parts, blocks);
     return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@
 #include "tt_assemble.h"
 #include "tt_build.h"
 #include "tt_ctx.h"
+#include "tt_refit_items_host.h"
 #include "tt_tlas_host.h"
 
 namespace {
@@ -1087,6 +1088,243 @@ tt_status tt_blas_refit(tt_ctx* c, const tt_blas_refit_params* p, const float* v
     TT_HIP(c, ring_close(c, c->timing, slot));
     TT_HIP(c, sw.end());
     if (!(p->flags & TT_TRACE_ASYNC) || !dev) TT_HIP(c, hipStreamSynchronize(c->stream));
+    return TT_OK;
+}
+
+tt_status tt_blas_refit_items_validate(const tt_blas_refit_item* items, uint32_t n_items, const tt_mesh_data* md,
+                                       uint32_t n_mesh, uint32_t n_scene_tris, uint32_t flags, char* why, uint32_t why_len) {
+    std::string w;
+    const tt_status st = tt_refit_items::check(items, n_items, md, n_mesh, n_scene_tris, flags, w);
+    copy_why(w, why, why_len);
+    return st;
+}
+
+namespace {
+// The composed plan of an item list: per-mesh host plans (built once per scene generation), one forest on the
+// device, the box pool. Called only when the list or the scene changed; nothing is enqueued by it.
+tt_status compose_refit_many(tt_ctx* c, const tt_blas_refit_item* items, uint32_t n_items, const std::vector<uint32_t>& key) {
+    tt_ctx::BlasRefitMany& M = c->refit_many;
+    std::vector<RefitForestItem> forest(n_items);
+    std::vector<uint32_t> box_base(n_items);
+    uint64_t n_pairs = 0;
+    uint32_t total = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> spans;  // [first node, end) of each item's BLAS
+    for (uint32_t i = 0; i < n_items; i++) {
+        const tt_mesh_data& md = c->host.mesh[items[i].mesh_index];
+        const uint32_t node_base = (uint32_t)md.NodeOffset;
+        tt_ctx::BlasPlanHost& P = c->many_plans[items[i].mesh_index];
+        if (P.gen != c->scene_gen || P.node_base != node_base) {
+            P.gen = ~0ull;
+            if (!tt_refit_build_plan(c->host.nodes.data() + node_base, (uint32_t)(c->host.nodes.size() - node_base), P.plan))
+                return fail(c, TT_ERR_INVALID_ARG, "tt_blas_refit_many: item %u: a BLAS child index leaves the node array", i);
+            P.n_nodes = 0;
+            for (int32_t b : P.plan.pair_bvh) P.n_nodes = std::max(P.n_nodes, (uint32_t)b + 1u);
+            P.gen = c->scene_gen;
+            P.node_base = node_base;
+        }
+        if ((uint32_t)P.plan.leaf_end > items[i].n_tris)
+            return fail(c, TT_ERR_INVALID_ARG, "tt_blas_refit_many: item %u: the BLAS references triangle %d beyond n_tris", i,
+                        P.plan.leaf_end - 1);
+        forest[i] = RefitForestItem{&P.plan, node_base, P.n_nodes, total};
+        box_base[i] = total;
+        total += items[i].n_tris;
+        n_pairs += P.plan.pair_bvh.size();
+        spans.emplace_back(node_base, node_base + P.n_nodes);
+    }
+    // the kernel-layout node copy is refreshed per BLAS, adjacent ones as one range: never the BLASes in between
+    std::sort(spans.begin(), spans.end());
+    std::vector<std::pair<uint32_t, uint32_t>> ranges;
+    for (const auto& s : spans) {
+        if (!ranges.empty() && s.first <= ranges.back().second)
+            ranges.back().second = std::max(ranges.back().second, s.second);
+        else
+            ranges.push_back(s);
+    }
+    if (n_pairs >= (1ull << 26))
+        return fail(c, TT_ERR_INVALID_ARG, "tt_blas_refit_many: the composed plan has %llu NodePairs (limit 2^26)",
+                    (unsigned long long)n_pairs);
+    M.gen = ~0ull;
+    TT_HIP(c, hipStreamSynchronize(c->stream));  // the old plan's buffers may be in use
+    TT_HIP(c, tt_refit_prepare_forest(forest, M.dev));
+    if (M.boxes.n < (size_t)6 * total) TT_HIP(c, M.boxes.alloc((size_t)6 * total));
+    M.key = key;
+    M.box_base = std::move(box_base);
+    M.node_ranges = std::move(ranges);
+    M.gen = c->scene_gen;
+    return TT_OK;
+}
+}  // namespace
+
+tt_status tt_blas_refit_many(tt_ctx* c, const tt_blas_refit_item* items, uint32_t n_items, uint32_t flags, float* bounds_out,
+                             float* mesh_aabbs) {
+    if (!c) return TT_ERR_INVALID_ARG;
+    TT_REFUSE_DEAD_STREAM(c);
+    TT_REFUSE_BORROWER(c);
+    if (!c->has_scene) return fail(c, TT_ERR_NO_SCENE, "no scene uploaded");
+    if (flags & ~(uint32_t)(TT_TRACE_DEVICE_PTRS | TT_TRACE_ASYNC)) return fail(c, TT_ERR_INVALID_ARG, "tt_blas_refit_many: unknown flag");
+    {
+        std::string why;
+        const tt_status st = tt_refit_items::check(items, n_items, c->host.mesh.data(), (uint32_t)c->host.mesh.size(),
+                                                   c->host.n_tris, flags, why);
+        if (st != TT_OK) return fail(c, st, "tt_blas_refit_many: %s", why.c_str());
+    }
+    const bool dev = (flags & TT_TRACE_DEVICE_PTRS) != 0;
+    uint32_t n_parts = 0, n_blocks = 0;
+    size_t n_vtx = 0, n_idx = 0, n_leaf = 0;  // what a host-pointer call stages, in elements
+    for (uint32_t i = 0; i < n_items; i++) {
+        const tt_blas_refit_item& it = items[i];
+        if ((uint32_t)c->host.mesh[it.mesh_index].NodeOffset >= c->host.nodes.size())
+            return fail(c, TT_ERR_INVALID_ARG, "tt_blas_refit_many: item %u: the record's NodeOffset %d lies beyond the scene's %zu nodes", i,
+                        c->host.mesh[it.mesh_index].NodeOffset, c->host.nodes.size());
+        if (dev && !is_device_ptr(it.leaf_of_triangle))
+            return fail(c, TT_ERR_INVALID_ARG, "tt_blas_refit_many: item %u: TT_TRACE_DEVICE_PTRS set but leaf_of_triangle is not device memory", i);
+        n_leaf += it.n_tris;
+        for (uint32_t k = 0; k < it.n_parts; k++) {
+            const tt_blas_refit_part& p = it.parts[k];
+            if (dev && !(is_device_ptr(p.vertices) && is_device_ptr(p.indices)))
+                return fail(c, TT_ERR_INVALID_ARG, "tt_blas_refit_many: item %u part %u: TT_TRACE_DEVICE_PTRS set but an array is not device memory", i, k);
+            n_blocks += (p.n_tris + 255u) / 256u;
+            n_vtx += (size_t)p.n_vertices * p.vertex_stride;
+            n_idx += (size_t)3 * p.n_tris;
+        }
+        n_parts += it.n_parts;
+    }
+    if (dev && ((bounds_out && !is_device_ptr(bounds_out)) || (mesh_aabbs && !is_device_ptr(mesh_aabbs))))
+        return fail(c, TT_ERR_INVALID_ARG, "tt_blas_refit_many: TT_TRACE_DEVICE_PTRS set but bounds_out or mesh_aabbs is not device memory");
+    TT_HIP(c, hipSetDevice(c->device));
+    tt_ctx::BlasRefitMany& M = c->refit_many;
+    {
+        // (the record's NodeOffset is part of the key: tt_scene_update_meshdata may re-point a record at another
+        // BLAS without a new scene generation, and the forest addresses nodes)
+        bool same = M.gen == c->scene_gen && M.key.size() == (size_t)3 * n_items;
+        for (uint32_t i = 0; same && i < n_items; i++)
+            same = M.key[3 * i] == items[i].mesh_index && M.key[3 * i + 1] == items[i].n_tris &&
+                   M.key[3 * i + 2] == (uint32_t)c->host.mesh[items[i].mesh_index].NodeOffset;
+        if (!same) {
+            std::vector<uint32_t> key((size_t)3 * n_items);
+            for (uint32_t i = 0; i < n_items; i++) {
+                key[3 * i] = items[i].mesh_index;
+                key[3 * i + 1] = items[i].n_tris;
+                key[3 * i + 2] = (uint32_t)c->host.mesh[items[i].mesh_index].NodeOffset;
+            }
+            const tt_status st = compose_refit_many(c, items, n_items, key);
+            if (st != TT_OK) return st;
+        }
+    }
+    // ---- host arrays: staged into the context's buffers (sized first: growing one drops what it held)
+    const float* d_vtx = nullptr;
+    const int32_t *d_idx = nullptr, *d_leaf = nullptr;
+    float *d_bounds = bounds_out, *d_aabbs = mesh_aabbs;
+    const size_t n_mesh = c->host.mesh.size();
+    if (!dev) {
+        TT_HIP(c, stage_in(c, c->st_vtx, nullptr, n_vtx, 0, d_vtx));
+        TT_HIP(c, stage_in(c, c->st_idx, nullptr, n_idx, 0, d_idx));
+        TT_HIP(c, stage_in(c, c->st_leaf, nullptr, n_leaf, 0, d_leaf));
+        if (bounds_out) {
+            if (M.bounds.n < (size_t)6 * n_items) TT_HIP(c, M.bounds.alloc((size_t)6 * n_items));
+            d_bounds = M.bounds.p;
+        }
+        if (mesh_aabbs) {
+            const float* in = nullptr;
+            TT_HIP(c, stage_in(c, c->st_boxes, mesh_aabbs, 6 * n_mesh, 0, in));  // the slots no item writes keep their values
+            d_aabbs = c->st_boxes.p;
+        }
+    }
+    // ---- the call's descriptors, composed in the pinned slot and copied to the device on the stream. One mesh of
+    // one renderer takes tt_blas_refit's own Construct kernel and carries its item in the refit's kernel arguments:
+    // no staging and no copy, so the batch form costs the one-mesh case nothing (profiles/r19/refit_batch)
+    const bool direct = n_items == 1 && n_parts == 1;
+    const size_t items_off = (size_t)n_parts * sizeof(RefitManyPart), blocks_off = items_off + (size_t)n_items * sizeof(RefitManyItem);
+    const size_t bytes = blocks_off + (size_t)n_blocks * sizeof(RefitManyBlock);
+    RefitManyPart one_part;
+    RefitManyItem one_item;
+    void* pinned = nullptr;
+    if (!direct) {
+        if (M.desc.n < bytes) TT_HIP(c, M.desc.alloc(bytes + bytes / 2));
+        TT_HIP(c, stage_begin(c, nullptr, bytes, pinned));
+    }
+    RefitManyPart* hp = direct ? &one_part : static_cast<RefitManyPart*>(pinned);
+    RefitManyItem* hi = direct ? &one_item : reinterpret_cast<RefitManyItem*>(static_cast<uint8_t*>(pinned) + items_off);
+    RefitManyBlock* hb = direct ? nullptr : reinterpret_cast<RefitManyBlock*>(static_cast<uint8_t*>(pinned) + blocks_off);
+    size_t o_vtx = 0, o_idx = 0, o_leaf = 0;
+    uint32_t part = 0, block = 0;
+    for (uint32_t i = 0; i < n_items; i++) {
+        const tt_blas_refit_item& it = items[i];
+        const uint32_t tri_base = (uint32_t)c->host.mesh[it.mesh_index].TriOffset;
+        const int32_t* leaf = it.leaf_of_triangle;
+        if (!dev) {
+            TT_HIP(c, hipMemcpyAsync(c->st_leaf.p + o_leaf, it.leaf_of_triangle, sizeof(int32_t) * it.n_tris, hipMemcpyHostToDevice, c->stream));
+            leaf = d_leaf + o_leaf;
+            o_leaf += it.n_tris;
+        }
+        for (uint32_t k = 0; k < it.n_parts; k++, part++) {
+            const tt_blas_refit_part& p = it.parts[k];
+            RefitManyPart& a = hp[part];
+            a.vertices = p.vertices;
+            a.indices = p.indices;
+            if (!dev) {
+                const size_t nv = (size_t)p.n_vertices * p.vertex_stride, ni = (size_t)3 * p.n_tris;
+                TT_HIP(c, hipMemcpyAsync(c->st_vtx.p + o_vtx, p.vertices, sizeof(float) * nv, hipMemcpyHostToDevice, c->stream));
+                TT_HIP(c, hipMemcpyAsync(c->st_idx.p + o_idx, p.indices, sizeof(int32_t) * ni, hipMemcpyHostToDevice, c->stream));
+                a.vertices = d_vtx + o_vtx;
+                a.indices = d_idx + o_idx;
+                o_vtx += nv;
+                o_idx += ni;
+            }
+            a.leaf_of = leaf + p.first_tri;
+            a.boxes = M.boxes.p + (size_t)6 * M.box_base[i];
+            a.tris88 = c->scene.tris_raw.p + tri_base;
+            a.tripos = c->scene.tris.p + tri_base;
+            a.n_tris = p.n_tris;
+            a.n_vertices = p.n_vertices;
+            a.vertex_stride = p.vertex_stride;
+            a.leaf_bound = it.n_tris;
+            std::memcpy(a.m, p.transform, sizeof(a.m));
+            for (uint32_t first = 0; hb && first < p.n_tris; first += 256u) hb[block++] = RefitManyBlock{part, first};
+        }
+        RefitManyItem& r = hi[i];
+        std::memset(&r, 0, sizeof(r));
+        r.mesh_index = it.mesh_index;
+        r.has_l2w = it.local_to_world != nullptr;
+        if (it.local_to_world) std::memcpy(r.l2w, it.local_to_world, sizeof(r.l2w));
+    }
+    if (!direct) {
+        TT_HIP(c, hipMemcpyAsync(M.desc.p, pinned, bytes, hipMemcpyHostToDevice, c->stream));
+        TT_HIP(c, stage_end(c));
+    }
+    uint32_t slot;
+    SceneWrite sw(c, true);
+    TT_HIP(c, sw.err);
+    TT_HIP(c, ring_open(c, c->timing, slot));
+    if (direct) {
+        BlasConstructArgs a{};
+        a.vertices = one_part.vertices;
+        a.indices = one_part.indices;
+        a.leaf_of = one_part.leaf_of;
+        a.n_tris = one_part.n_tris;  // (= the item's count: the one part tiles the mesh)
+        a.n_vertices = one_part.n_vertices;
+        a.vertex_stride = one_part.vertex_stride;
+        std::memcpy(a.m, one_part.m, sizeof(a.m));
+        a.boxes = one_part.boxes;
+        a.tris88 = one_part.tris88;
+        a.tripos = one_part.tripos;
+        TT_HIP(c, tt_blas_construct(a, c->stream));
+        TT_HIP(c, tt_refit_run_forest(M.dev, M.boxes.p, c->scene.nodes.p, nullptr, &one_item, d_bounds, d_aabbs, c->stream));
+    } else {
+        TT_HIP(c, tt_blas_construct_many(reinterpret_cast<const RefitManyPart*>(M.desc.p),
+                                         reinterpret_cast<const RefitManyBlock*>(M.desc.p + blocks_off), n_blocks, c->stream));
+        TT_HIP(c, tt_refit_run_forest(M.dev, M.boxes.p, c->scene.nodes.p, reinterpret_cast<const RefitManyItem*>(M.desc.p + items_off),
+                                      nullptr, d_bounds, d_aabbs, c->stream));
+    }
+    if (TT_NODE_STRIDE != 80)
+        for (const auto& r : M.node_ranges) TT_HIP(c, refresh_node_copy(c, r.first, r.second - r.first));
+    TT_HIP(c, ring_close(c, c->timing, slot));
+    TT_HIP(c, sw.end());
+    if (!dev) {
+        if (bounds_out) TT_HIP(c, stage_out(c, bounds_out, d_bounds, (size_t)6 * n_items));
+        if (mesh_aabbs) TT_HIP(c, stage_out(c, mesh_aabbs, d_aabbs, 6 * n_mesh));
+    }
+    if (!(flags & TT_TRACE_ASYNC) || !dev) TT_HIP(c, hipStreamSynchronize(c->stream));
     return TT_OK;
 }
 

@@ -116,6 +116,17 @@ class BlasRefitParams(C.Structure):
                 ("vertex_stride", C.c_uint32), ("transform", C.c_float * 16), ("flags", C.c_uint32)]
 
 
+class BlasRefitPart(C.Structure):
+    _fields_ = [("vertices", C.c_void_p), ("n_vertices", C.c_uint32), ("vertex_stride", C.c_uint32),
+                ("indices", C.c_void_p), ("n_tris", C.c_uint32), ("first_tri", C.c_uint32),
+                ("transform", C.c_float * 16)]
+
+
+class BlasRefitItem(C.Structure):
+    _fields_ = [("mesh_index", C.c_uint32), ("n_tris", C.c_uint32), ("leaf_of_triangle", C.c_void_p),
+                ("parts", C.POINTER(BlasRefitPart)), ("n_parts", C.c_uint32), ("local_to_world", C.c_void_p)]
+
+
 class TraceParams(C.Structure):
     _fields_ = [("n_rays", C.c_uint32), ("bounce", C.c_int32), ("far_plane", C.c_float),
                 ("screen_width", C.c_uint32), ("screen_height", C.c_uint32), ("flags", C.c_uint32)]
@@ -220,7 +231,7 @@ HIP_SYMBOLS = ["tt_abi_version", "tt_device_count", "tt_ctx_create", "tt_ctx_des
                "tt_object_destroy", "tt_scene_layout_objects", "tt_scene_layout_counts", "tt_scene_assemble_objects",
                "tt_object_build_device", "tt_object_read", "tt_object_leaf_order_device", "tt_objects_build_device",
                "tt_scene_update_tlas", "tt_tlas_rebuild", "tt_scene_read_tlas_indices", "tt_group_tlas_rebuild",
-               "tt_group_scene_update_tlas"]
+               "tt_group_scene_update_tlas", "tt_blas_refit_many", "tt_blas_refit_items_validate"]
 SCENE_SYMBOLS = ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_blas_free", "tt_scene_assemble",
                  "tt_scene_build_get_info", "tt_scene_build_copy", "tt_scene_build_free", "tt_pack_octahedral",
                  "tt_bvh2_build", "tt_dotnet_sort_by_key", "tt_synth_cornell", "tt_synth_soup", "tt_synth_sponza",
@@ -389,6 +400,11 @@ def hip_lib():
         L.tt_scene_read_nodes.argtypes = [vp, u32, u32, vp]
         L.tt_scene_read_tris.argtypes = [vp, u32, u32, vp]
         L.tt_blas_refit.argtypes = [vp, C.POINTER(BlasRefitParams), vp, vp, vp]
+        if hasattr(L, "tt_blas_refit_many"):  # (absent from older libraries)
+            L.tt_blas_refit_many.argtypes = [vp, C.POINTER(BlasRefitItem), u32, u32, vp, vp]
+            L.tt_blas_refit_items_validate.argtypes = [C.POINTER(BlasRefitItem), u32, vp, u32, u32, u32, C.c_char_p, u32]
+            for s in ["tt_blas_refit_many", "tt_blas_refit_items_validate"]:
+                getattr(L, s).restype = i32
         L.tt_bvh2_build_device.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(u32)]
         L.tt_blas_build_device.argtypes = [vp, vp, u32, vp, vp, u32, C.POINTER(u32), vp, C.POINTER(u32)]
         L.tt_bvh2_presort_device.argtypes = [vp, vp, u32, vp]
@@ -1054,6 +1070,69 @@ def _object_handles(objects):
     return (C.c_void_p * max(1, len(objects)))(*[o.h if o is not None else None for o in objects])
 
 
+class RefitPart:
+    """One renderer of a deforming mesh (tt_blas_refit_part): `vertices` n x stride floats (position at +0, normal
+    at +3), `indices` 3 per triangle local to it, `first_tri` its place among the mesh's source triangles,
+    `transform` a row-major 4x4 (identity by default). Arrays are numpy arrays or device tensors."""
+
+    def __init__(self, vertices, indices, first_tri: int = 0, transform=None, n_vertices=None, vertex_stride=None,
+                 n_tris=None):
+        two_d = hasattr(vertices, "shape") and len(vertices.shape) == 2
+        self.vertices, self.indices, self.first_tri = vertices, indices, int(first_tri)
+        self.n_vertices = int(n_vertices if n_vertices is not None else vertices.shape[0] if two_d else 0)
+        self.vertex_stride = int(vertex_stride if vertex_stride is not None else vertices.shape[1] if two_d else 6)
+        if n_tris is None:
+            shape = getattr(indices, "shape", None)
+            n_tris = 0 if not shape else int(shape[0]) // 3 if len(shape) == 1 else int(shape[0])
+        self.n_tris = int(n_tris)
+        self.transform = np.eye(4) if transform is None else np.asarray(transform)
+
+
+class RefitItem:
+    """One deforming mesh (tt_blas_refit_item): its _MeshData record, its BLAS's triangle count, leaf_of_triangle
+    (Blas.leaf_order() or an object's leaf_order_device), its parts and, optionally, the row-major local_to_world
+    whose world box goes to mesh_aabbs[mesh_index]."""
+
+    def __init__(self, mesh_index: int, n_tris: int, leaf_of_triangle, parts, local_to_world=None):
+        self.mesh_index, self.n_tris, self.leaf_of_triangle = int(mesh_index), int(n_tris), leaf_of_triangle
+        self.parts, self.local_to_world = list(parts), local_to_world
+
+
+def refit_item_array(items):
+    """(ctypes array of tt_blas_refit_item, the objects that must outlive the call)."""
+    arr = (BlasRefitItem * max(1, len(items)))()
+    keep = []
+    for i, it in enumerate(items):
+        parts = (BlasRefitPart * max(1, len(it.parts)))()
+        for k, p in enumerate(it.parts):
+            parts[k].vertices, parts[k].indices = _ptr(p.vertices), _ptr(p.indices)
+            parts[k].n_vertices, parts[k].vertex_stride = p.n_vertices, p.vertex_stride
+            parts[k].n_tris, parts[k].first_tri = p.n_tris, p.first_tri
+            parts[k].transform[:] = unity_colmajor(p.transform)
+        arr[i].mesh_index, arr[i].n_tris = it.mesh_index, it.n_tris
+        arr[i].leaf_of_triangle = _ptr(it.leaf_of_triangle)
+        arr[i].parts = parts if it.parts else None
+        arr[i].n_parts = len(it.parts)
+        if it.local_to_world is not None:
+            m = np.ascontiguousarray(unity_colmajor(np.asarray(it.local_to_world)), np.float32)
+            arr[i].local_to_world = m.ctypes.data
+            keep.append(m)
+        keep.append(parts)
+    return arr, keep
+
+
+def blas_refit_items_validate(items, meshdata: np.ndarray, n_scene_tris: int, device: bool = False):
+    """tt_blas_refit_items_validate (host only): (status, first violation) of an item list against a scene's
+    _MeshData records and triangle count."""
+    arr, keep = refit_item_array(items)
+    md = np.ascontiguousarray(meshdata, MESH_DTYPE)
+    why = C.create_string_buffer(256)
+    st = hip_lib().tt_blas_refit_items_validate(arr if items else None, len(items), _ptr(md), len(md), int(n_scene_tris),
+                                                TT_TRACE_DEVICE_PTRS if device else 0, why, 256)
+    del keep
+    return st, why.value.decode()
+
+
 def object_validate(nodes: np.ndarray, tris: np.ndarray, root: int = 0):
     """tt_object_validate (host only): (status, first violation) of one BLAS's arrays against its own counts."""
     nodes, tris = np.ascontiguousarray(nodes, NODE_DTYPE), np.ascontiguousarray(tris, TRI_DTYPE)
@@ -1485,6 +1564,19 @@ class Engine:
         p.transform[:] = unity_colmajor(np.eye(4) if transform is None else np.asarray(transform))
         self._check(self.L.tt_blas_refit(self.h, C.byref(p), _ptr(vertices), _ptr(indices), _ptr(leaf_of_triangle)),
                     "tt_blas_refit")
+
+    def blas_refit_many(self, items, device: bool = False, asynchronous: bool = False, bounds_out=None,
+                        mesh_aabbs=None, check: bool = True) -> int:
+        """tt_blas_refit_many (ParentObject.RefitMesh for a frame's deforming meshes, renderer by renderer): `items`
+        is a list of RefitItem. bounds_out (n_items x 6) and mesh_aabbs (n_mesh x 6, the array tlas_refit takes)
+        are written in place: numpy arrays, or device tensors with device=True."""
+        arr, keep = refit_item_array(items)
+        flags = (TT_TRACE_DEVICE_PTRS if device else 0) | (TT_TRACE_ASYNC if asynchronous else 0)
+        st = self.L.tt_blas_refit_many(self.h, arr, len(items), flags, _ptr(bounds_out), _ptr(mesh_aabbs))
+        del keep
+        if check:
+            self._check(st, "tt_blas_refit_many")
+        return st
 
     def scene_tris(self, first: int, count: int) -> np.ndarray:
         """Reads AggTris [first, first+count) back from HBM (parity checks of the BLAS refit)."""
