@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import enclosure
 import handbuilt as hb
 import kat_cases as K
 import tthip
@@ -35,6 +36,9 @@ def decode_nodes(nodes):
 
 
 def check_blas(nodes, tris, padded_aabbs=None):
+    """Structure per node here; enclosure within 2 U of every leaf slot here and of every slot, inner ones included,
+    in the float64 model (tests/enclosure.py, where U and the limit are derived). Never looser than the
+    1e-4 * (1 + |b|) this function used before."""
     dec = decode_nodes(nodes)
     seen = np.zeros(len(tris), np.int32)
     for p, e, imask, bc, bt, kids in dec:
@@ -58,11 +62,14 @@ def check_blas(nodes, tris, padded_aabbs=None):
                     tr = tris[t]
                     v = np.stack([tr["pos0"], tr["pos0"] + tr["posedge1"], tr["pos0"] + tr["posedge2"]]).astype(np.float64)
                     # quantized child box is conservative for the triangle (floor/ceil quantization)
-                    assert (v.min(0) >= bmin - 1e-4 * (1 + np.abs(bmin))).all()
-                    assert (v.max(0) <= bmax + 1e-4 * (1 + np.abs(bmax))).all()
+                    tol = [enclosure.LIMIT_TRIS * enclosure.U24 * np.maximum(np.maximum(np.abs(x), np.abs(p)), 256 * scale)
+                           for x in (v.min(0), v.max(0))]
+                    assert (v.min(0) >= bmin - np.minimum(tol[0], 1e-4 * (1 + np.abs(bmin)))).all()
+                    assert (v.max(0) <= bmax + np.minimum(tol[1], 1e-4 * (1 + np.abs(bmax)))).all()
         assert ntri <= 24
         assert sorted(inner_seen) == list(range(n_inner))
     assert (seen == 1).all(), "every triangle referenced by exactly one leaf"
+    enclosure.blas(nodes, tris).check()
 
 
 def test_cornell_blas():
