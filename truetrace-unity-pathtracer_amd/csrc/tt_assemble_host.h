@@ -1,6 +1,6 @@
 // tt_assemble_host.h — the host-only half of the GPU-resident objects (tt_object_*, tt_scene_layout_*):
-// the BLAS-level walk that validates one object against its own counts, and AccumulateData's running
-// sums. Plain C++ with no HIP in it, so a stand-alone program can run it under the host sanitizers
+// the BLAS-level walk that validates one object against its own counts (the shared loop of
+// tt_scene_check_host.h, with the object's bounds and messages), and AccumulateData's running sums. Plain C++ with no HIP in it, so a stand-alone program can run it under the host sanitizers
 // (tests/native/assemble_kat_main.cpp).
 #pragma once
 #include <cstdint>
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/truetrace_hip.h"
+#include "tt_scene_check_host.h"
 
 namespace tt_asm {
 
@@ -20,10 +21,45 @@ struct ObjectWalk {
     std::string why;
 };
 
-// Validator::walk at BLAS level with NodeOffset = TriOffset = 0 (IntersectBVH's index arithmetic,
-// IntersectionKernels.compute:157-213), bounded by the object's own counts: stricter than the whole-scene
+// The shared walk (tt_scene_check_host.h) at BLAS level with NodeOffset = TriOffset = 0 (IntersectBVH's index
+// arithmetic, IntersectionKernels.compute:157-213), bounded by the object's own counts: stricter than the whole-scene
 // check, where a BLAS may reach into its neighbours. tris == nullptr (the triangles exist on the device only,
 // tt_object_build_device): every index is checked as before, max_matdat is left at 0 for the caller to supply.
+struct ObjectLevel {
+    const uint32_t n_nodes;
+    const tt_cwbvh_node* nodes;
+    const tt_cuda_triangle* tris;
+    const uint32_t n_tris;
+    ObjectWalk& w;
+    static std::string of_node(uint32_t ni) { return " of node " + std::to_string(ni); }
+    TT_CHECK_INLINE tt_check::Enter enter(uint32_t ni) {  // (in range: the root and every child were checked before they were pushed)
+        if (w.reach[ni]) return tt_check::Enter::seen;
+        w.reach[ni] = 1u;
+        return tt_check::Enter::fresh;
+    }
+    const tt_cwbvh_node& node(uint32_t ni) const { return nodes[ni]; }
+    TT_CHECK_INLINE bool child(uint32_t ni, const tt_cwbvh_node& n, uint32_t rank, uint32_t& out) {
+        const uint64_t child = (uint64_t)n.base_child + rank;
+        out = (uint32_t)child;
+        if (child < n_nodes) return true;
+        w.why = "child index " + std::to_string(child) + of_node(ni) + " outside the object's " + std::to_string(n_nodes) + " nodes";
+        return false;
+    }
+    TT_CHECK_INLINE bool leaf(uint32_t ni, uint64_t t) {
+        if (t >= n_tris) {
+            w.why = "triangle index " + std::to_string(t) + of_node(ni) + " outside the object's " + std::to_string(n_tris) +
+                    " triangles";
+            return false;
+        }
+        w.leaf_tris++;
+        if (tris && tris[t].MatDat > w.max_matdat) w.max_matdat = tris[t].MatDat;
+        return true;
+    }
+    bool bad_meta(uint32_t ni, const char* what) {
+        w.why = std::string(what) + " (node " + std::to_string(ni) + ")";
+        return false;
+    }
+};
 inline bool walk_object(const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_cuda_triangle* tris, uint32_t n_tris,
                         uint32_t root, ObjectWalk& w) {
     w.reach.assign(n_nodes, 0u);
@@ -33,51 +69,8 @@ inline bool walk_object(const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_c
         w.why = "root " + std::to_string(root) + " outside the object's " + std::to_string(n_nodes) + " nodes";
         return false;
     }
-    std::vector<uint32_t> work{root};
-    while (!work.empty()) {
-        const uint32_t ni = work.back();
-        work.pop_back();
-        if (w.reach[ni]) continue;
-        w.reach[ni] = 1u;
-        const tt_cwbvh_node& n = nodes[ni];
-        const uint32_t imask = n.e_imask >> 24;
-        for (int k = 0; k < 8; k++) {
-            const uint32_t meta = (n.meta[k >> 2] >> ((k & 3) * 8)) & 0xffu;
-            const uint32_t low5 = meta & 0x1fu, bits = (meta >> 5) & 7u;
-            if ((meta & 0x18u) == 0x18u) {
-                if (bits != 1u) {
-                    w.why = "inner meta with child bits != 1 (node " + std::to_string(ni) + ")";
-                    return false;
-                }
-                const uint32_t slot = low5 - 24u;
-                const uint64_t child = (uint64_t)n.base_child + (uint32_t)__builtin_popcount(imask & ((1u << slot) - 1u));
-                if (child >= n_nodes) {
-                    w.why = "child index " + std::to_string(child) + " of node " + std::to_string(ni) +
-                            " outside the object's " + std::to_string(n_nodes) + " nodes";
-                    return false;
-                }
-                work.push_back((uint32_t)child);
-            } else if (bits) {
-                const uint32_t top = low5 + (31u - (uint32_t)__builtin_clz(bits));
-                if (top >= 24u) {
-                    w.why = "leaf meta spills into the internal-child bits (node " + std::to_string(ni) + ")";
-                    return false;
-                }
-                for (uint32_t b = 0; b < 3; b++) {
-                    if (!((bits >> b) & 1u)) continue;
-                    const uint64_t t = (uint64_t)n.base_tri + low5 + b;
-                    if (t >= n_tris) {
-                        w.why = "triangle index " + std::to_string(t) + " of node " + std::to_string(ni) +
-                                " outside the object's " + std::to_string(n_tris) + " triangles";
-                        return false;
-                    }
-                    w.leaf_tris++;
-                    if (tris && tris[t].MatDat > w.max_matdat) w.max_matdat = tris[t].MatDat;
-                }
-            }
-        }
-    }
-    return true;
+    ObjectLevel p{n_nodes, nodes, tris, n_tris, w};
+    return tt_check::walk(root, p);
 }
 
 inline tt_status validate_object(const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_cuda_triangle* tris,

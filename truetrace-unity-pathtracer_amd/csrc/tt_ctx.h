@@ -1,6 +1,8 @@
 // tt_ctx.h — internal to the C ABI's translation units (tt_api.hip, tt_scene_api.hip, tt_dispatch.hip,
 // tt_build.hip; not installed): the context and object structs, the owning device buffer, error reporting,
 // the shared-scene read / write sections, the timing-ring entries and the host-pointer staging helpers.
+// The structural checks of what a kernel may reach are host-only headers with no HIP in them:
+// tt_scene_check_host.h (the one CWBVH walk, the whole-scene check), tt_assemble_host.h, tt_tlas_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -79,33 +81,19 @@ struct DevBuf {
 static_assert(!std::is_copy_constructible<DevBuf<int>>::value, "DevBuf owns its allocation");
 static_assert(std::is_nothrow_move_constructible<DevBuf<int>>::value, "DevBuf moves without throwing");
 
-struct SceneHost {
+// The host mirror of a scene, with what its last validation established (tt_check::Bookkeeping: blas_ok,
+// is_tlas_node, tlas_nodes, is_blas_node) for the incremental per-frame updates (tt_scene_update_*)
+struct SceneHost : tt_check::Bookkeeping {
     std::vector<tt_cwbvh_node> nodes;
     std::vector<int32_t> tlas;
     std::vector<tt_mesh_data> mesh;
     uint32_t n_tris = 0;
     uint32_t n_mat = 0;
-    std::vector<uint32_t> matdat;  // only kept when a material sets the Invisible flag
     bool any_shadow_skip = false;  // IsBackground / ShadowCaster present (shadow material checks)
     bool any_atlas_shadow = false; // specTrans == 1 present (shadow glass tint: needs the texture atlas)
     bool any_cutout = false;       // Cutout materials present (need the alpha atlas)
     std::vector<CutoutMat> cut;    // per material, when any_cutout
     std::vector<GlassMat> glass;   // per material, when any_atlas_shadow
-    // incremental per-frame updates (tt_scene_update_*): what the last full validation established
-    struct BlasKey {
-        uint32_t root, node_offset, tri_offset;
-        bool operator<(const BlasKey& o) const {
-            return root != o.root ? root < o.root : node_offset != o.node_offset ? node_offset < o.node_offset
-                                                                                  : tri_offset < o.tri_offset;
-        }
-        bool operator==(const BlasKey& o) const {
-            return root == o.root && node_offset == o.node_offset && tri_offset == o.tri_offset;
-        }
-    };
-    std::vector<BlasKey> blas_ok;       // sorted: (root, NodeOffset, TriOffset) triples walked and valid
-    std::vector<uint8_t> is_tlas_node;  // node reached by the TLAS-level walk
-    std::vector<uint32_t> tlas_nodes;   // the same, as a list
-    std::vector<uint8_t> is_blas_node;  // node reached by a validated BLAS walk (never TLAS-only updated)
 };
 
 // A scene's device buffers. The one list of them: what an upload replaces, what a borrower borrows and what

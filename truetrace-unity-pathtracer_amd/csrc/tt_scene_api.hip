@@ -14,157 +14,21 @@
 
 namespace {
 
-// Structural validation of everything the trace kernel can reach (IntersectBVH's index
-// arithmetic, IntersectionKernels.compute:157-213): every reachable node, triangle, TLAS slot
-// and mesh record must be in range, so the GPU kernel needs no per-access bounds checks.
-struct Validator {
-    const SceneHost& s;
-    // the nodes a walk reads: TLAS-level walks tl[0, n_tl), BLAS-level walks bl[0, n_bl). A context's own
-    // scene: both are its host.nodes. An overlay borrower (tt_ctx_share_blas): its TLAS copy, and the lender's
-    // nodes and material words, exactly as its kernels address them (TLAS at tlas_base, BLASes shared).
-    const tt_cwbvh_node* tl;
-    uint32_t n_tl;
-    const tt_cwbvh_node* bl;
-    uint32_t n_bl;
-    const std::vector<uint32_t>* matdat;
-    std::vector<uint32_t> epoch_of;
-    uint32_t epoch = 0;
-    std::string why;
-    explicit Validator(const SceneHost& h)
-        : s(h), tl(h.nodes.data()), n_tl((uint32_t)h.nodes.size()), bl(h.nodes.data()), n_bl((uint32_t)h.nodes.size()),
-          matdat(&h.matdat), epoch_of(h.nodes.size(), 0u) {}
-    Validator(const SceneHost& own, const SceneHost& blas)
-        : s(own), tl(own.nodes.data()), n_tl((uint32_t)own.nodes.size()), bl(blas.nodes.data()),
-          n_bl((uint32_t)blas.nodes.size()), matdat(&blas.matdat),
-          epoch_of(std::max(own.nodes.size(), blas.nodes.size()), 0u) {}
+using tt_check::Validator;
 
-    uint32_t max_matdat = 0;
-    std::vector<uint32_t> tlas_visit;  // nodes reached by the last TLAS-level walk
-    std::vector<uint32_t> blas_visit;  // nodes reached by the BLAS-level walks of this validator
-    std::vector<SceneHost::BlasKey> keys;  // BLAS (root, NodeOffset, TriOffset) walked by run()
-    bool walk(uint32_t root, uint32_t node_offset, uint32_t tri_offset, bool tlas_level) {
-        epoch++;
-        max_matdat = 0;
-        if (tlas_level) tlas_visit.clear();
-        std::vector<uint32_t> work{root};
-        while (!work.empty()) {
-            const uint32_t ni = work.back();
-            work.pop_back();
-            if (ni >= (tlas_level ? n_tl : n_bl)) {
-                why = "node index " + std::to_string(ni) + " out of range" +
-                      (tlas_level && tl != bl ? " of the context's own TLAS nodes" : "");
-                return false;
-            }
-            if (epoch_of[ni] == epoch) continue;
-            epoch_of[ni] = epoch;
-            if (tlas_level) tlas_visit.push_back(ni);
-            else blas_visit.push_back(ni);
-            const tt_cwbvh_node& n = tlas_level ? tl[ni] : bl[ni];
-            const uint32_t imask = n.e_imask >> 24;
-            for (int k = 0; k < 8; k++) {
-                const uint32_t meta = (n.meta[k >> 2] >> ((k & 3) * 8)) & 0xffu;
-                const uint32_t low5 = meta & 0x1fu, bits = (meta >> 5) & 7u;
-                const bool inner = (meta & 0x18u) == 0x18u;
-                if (inner) {
-                    if (bits != 1u) {
-                        why = "inner meta with child bits != 1";
-                        return false;
-                    }
-                    const uint32_t slot = low5 - 24u;
-                    const uint32_t child = n.base_child + node_offset + (uint32_t)__builtin_popcount(imask & ((1u << slot) - 1u));
-                    work.push_back(child);
-                } else if (bits) {
-                    const uint32_t top = low5 + (31u - (uint32_t)__builtin_clz(bits));
-                    if (top >= 24u) {
-                        why = "leaf meta spills into the internal-child bits";
-                        return false;
-                    }
-                    for (uint32_t b = 0; b < 3; b++) {
-                        if (!((bits >> b) & 1u)) continue;
-                        const uint64_t t = (uint64_t)n.base_tri + tri_offset + low5 + b;
-                        if (tlas_level) {
-                            if (t >= s.tlas.size()) {
-                                why = "TLAS leaf slot out of range";
-                                return false;
-                            }
-                            const int32_t m = s.tlas[t];
-                            if (m < 0 || (size_t)m >= s.mesh.size()) {
-                                why = "TLASBVH8Indices entry out of range";
-                                return false;
-                            }
-                        } else if (t >= s.n_tris) {
-                            why = "triangle index out of range";
-                            return false;
-                        } else if (!matdat->empty()) {
-                            max_matdat = std::max(max_matdat, (*matdat)[(size_t)t]);
-                        }
-                    }
-                }
-            }
-        }
-        return true;
-    }
-
-    // one mesh record's BLAS (IntersectionKernels.compute:197-213 reach it through the TLAS)
-    bool walk_mesh(const tt_mesh_data& md) {
-        if (md.NodeOffset < 0 || md.TriOffset < 0) {
-            why = "negative mesh offsets";
-            return false;
-        }
-        return walk((uint32_t)(md.mesh_data_bvh_offsets & 0x7fffffff), (uint32_t)md.NodeOffset,
-                    (uint32_t)md.TriOffset, false);
-    }
-
-    bool run() {
-        if (n_tl == 0 || n_bl == 0 || s.mesh.empty()) {
-            why = "empty scene";
-            return false;
-        }
-        if (!walk(0, 0, 0, true)) return false;
-        // every mesh record reachable through the TLAS (validate them all: cheap, and update
-        // paths may re-point TLAS leaves)
-        struct Seen {
-            uint64_t key;
-            uint32_t root, max_matdat;
-        };
-        std::vector<Seen> seen;
-        for (size_t m = 0; m < s.mesh.size(); m++) {
-            const tt_mesh_data& md = s.mesh[m];
-            const uint32_t root = (uint32_t)(md.mesh_data_bvh_offsets & 0x7fffffff);
-            if (md.NodeOffset < 0 || md.TriOffset < 0) {
-                why = "negative mesh offsets";
-                return false;
-            }
-            const uint64_t key = ((uint64_t)(uint32_t)md.NodeOffset << 32) | (uint32_t)md.TriOffset;
-            uint32_t mm = 0;
-            bool dup = false;
-            for (auto& p : seen)
-                if (p.key == key && p.root == root) {
-                    dup = true;
-                    mm = p.max_matdat;
-                }
-            if (!dup) {
-                if (!walk(root, (uint32_t)md.NodeOffset, (uint32_t)md.TriOffset, false)) return false;
-                mm = max_matdat;
-                seen.push_back(Seen{key, root, mm});
-                keys.push_back(SceneHost::BlasKey{root, (uint32_t)md.NodeOffset, (uint32_t)md.TriOffset});
-            }
-
-        }
-        std::sort(keys.begin(), keys.end());
-        return true;
-    }
-};
-
-// Records what a full validation established, for the incremental per-frame update paths.
-void remember_validation(SceneHost& h, const Validator& v) {
-    h.blas_ok = v.keys;
-    h.is_tlas_node.assign(h.nodes.size(), 0u);
-    h.tlas_nodes = v.tlas_visit;
-    for (uint32_t n : h.tlas_nodes) h.is_tlas_node[n] = 1u;
-    h.is_blas_node.assign(h.nodes.size(), 0u);
-    for (uint32_t n : v.blas_visit) h.is_blas_node[n] = 1u;
+// What the whole-scene check (tt_scene_check_host.h) reads of a context's own scene ...
+tt_check::SceneView view_of(const SceneHost& h) {
+    const uint32_t n = (uint32_t)h.nodes.size();
+    return {h.nodes.data(), n, h.nodes.data(), n, h.tlas.data(), h.tlas.size(), h.mesh.data(), h.mesh.size(), h.n_tris};
 }
+// ... and of an overlay borrower (tt_ctx_share_blas): its own TLAS side over the lender's nodes
+tt_check::SceneView view_of(const SceneHost& own, const SceneHost& blas) {
+    tt_check::SceneView v = view_of(own);
+    v.bl = blas.nodes.data();
+    v.n_bl = (uint32_t)blas.nodes.size();
+    return v;
+}
+tt_check::SceneView view_of(const tt_ctx* c) { return c->ovl ? view_of(c->host, c->lender->host) : view_of(c->host); }
 
 // The material words and the cutout / glass records of a scene's materials (h starts out fresh), shared by the
 // two ways a scene arrives: tt_scene_upload and tt_scene_assemble_objects.
@@ -206,17 +70,28 @@ void derive_materials(const tt_material* mats, uint32_t n_mat, SceneHost& h, std
     }
 }
 
+const char kOver4GiB[] = "node or triangle array of 4 GiB or more (the trace kernel addresses them with 32-bit offsets)";
+bool over_4gib(uint64_t n_nodes, uint64_t n_tris) {
+    return n_nodes * std::max<uint64_t>(sizeof(tt_cwbvh_node), TT_NODE_STRIDE) >= (1ull << 32) || n_tris * 48u >= (1ull << 32);
+}
+
+// A scene's arrays as tt_scene_upload and tt_scene_validate take them: is one missing?
+bool null_or_empty(const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_cuda_triangle* tris, uint32_t n_tris,
+                   const int32_t* tlas, uint32_t n_tlas, const tt_mesh_data* md, uint32_t n_mesh, const tt_material* mats,
+                   uint32_t n_mat) {
+    return !nodes || !n_nodes || !tris || !n_tris || !tlas || !n_tlas || !md || !n_mesh || (n_mat && !mats);
+}
+
 tt_status check_scene(const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_cuda_triangle* tris, uint32_t n_tris,
                       const int32_t* tlas, uint32_t n_tlas, const tt_mesh_data* md, uint32_t n_mesh,
                       const tt_material* mats, uint32_t n_mat, SceneHost& h, std::vector<uint32_t>& tags,
                       bool& any_invisible, std::string& why) {
-    if (!nodes || !n_nodes || !tris || !n_tris || !tlas || !n_tlas || !md || !n_mesh || (n_mat && !mats)) {
+    if (null_or_empty(nodes, n_nodes, tris, n_tris, tlas, n_tlas, md, n_mesh, mats, n_mat)) {
         why = "null or empty buffer";
         return TT_ERR_INVALID_ARG;
     }
-    if ((uint64_t)n_nodes * std::max<uint64_t>(sizeof(tt_cwbvh_node), TT_NODE_STRIDE) >= (1ull << 32) ||
-        (uint64_t)n_tris * 48u >= (1ull << 32)) {
-        why = "node or triangle array of 4 GiB or more (the trace kernel addresses them with 32-bit offsets)";
+    if (over_4gib(n_nodes, n_tris)) {
+        why = kOver4GiB;
         return TT_ERR_INVALID_ARG;
     }
     h.nodes.assign(nodes, nodes + n_nodes);
@@ -224,16 +99,12 @@ tt_status check_scene(const tt_cwbvh_node* nodes, uint32_t n_nodes, const tt_cud
     h.mesh.assign(md, md + n_mesh);
     h.n_tris = n_tris;
     derive_materials(mats, n_mat, h, tags, any_invisible);
-    if (any_invisible) {
-        h.matdat.resize(n_tris);
-        for (uint32_t t = 0; t < n_tris; t++) h.matdat[t] = tris[t].MatDat;
-    }
-    Validator v(h);
+    Validator v(view_of(h));
     if (!v.run()) {
         why = v.why;
         return TT_ERR_INVALID_ARG;
     }
-    remember_validation(h, v);
+    tt_check::remember_validation(h, v, n_nodes);
     return TT_OK;
 }
 
@@ -371,10 +242,6 @@ bool assemble_kernel_form() {
     return !(e && std::strcmp(e, "memcpy") == 0);
 }
 
-bool over_4gib(uint64_t n_nodes, uint64_t n_tris) {
-    return n_nodes * std::max<uint64_t>(sizeof(tt_cwbvh_node), TT_NODE_STRIDE) >= (1ull << 32) || n_tris * 48u >= (1ull << 32);
-}
-
 // Installing a scene, the part tt_scene_upload and tt_scene_assemble_objects share: scene_alloc, then the caller
 // fills the node and triangle arrays its own way, then scene_commit. Whatever the caller's way, the context ends
 // up the same: same buffers, same sizes, same bookkeeping.
@@ -502,7 +369,7 @@ tt_status tt_scene_upload(tt_ctx* c, const tt_cwbvh_node* nodes, uint32_t n_node
     TT_REFUSE_DEAD_STREAM(c);
     TT_REFUSE_BORROWER(c);
     TT_REFUSE_LENDER(c);
-    if (!nodes || !n_nodes || !tris || !n_tris || !tlas || !n_tlas || !md || !n_mesh || (n_mat && !mats))
+    if (null_or_empty(nodes, n_nodes, tris, n_tris, tlas, n_tlas, md, n_mesh, mats, n_mat))
         return fail(c, TT_ERR_INVALID_ARG, "tt_scene_upload: null or empty buffer");
     TT_HIP(c, hipSetDevice(c->device));
     c->has_scene = false;
@@ -549,8 +416,7 @@ tt_status tt_object_create(tt_ctx* c, const tt_cwbvh_node* nodes, uint32_t n_nod
     std::unique_ptr<tt_object> o(new tt_object);
     const tt_status vs = tt_asm::validate_object(nodes, n_nodes, tris, n_tris, root, o->walk);
     if (vs != TT_OK) return fail(c, vs, "object validation failed: %s", o->walk.why.c_str());
-    if (over_4gib(n_nodes, n_tris))
-        return fail(c, TT_ERR_INVALID_ARG, "node or triangle array of 4 GiB or more (the trace kernel addresses them with 32-bit offsets)");
+    if (over_4gib(n_nodes, n_tris)) return fail(c, TT_ERR_INVALID_ARG, "%s", kOver4GiB);
     TT_HIP(c, hipSetDevice(c->device));
     hipError_t e;
     if ((e = o->d_nodes.alloc(n_nodes)) != hipSuccess || (e = o->d_tris.alloc(n_tris)) != hipSuccess ||
@@ -631,16 +497,14 @@ tt_status tt_scene_assemble_objects(tt_ctx* c, const tt_object* const* objects, 
     if (tt_asm::layout_counts(cnt_n.data(), cnt_t.data(), n_objects, tlas_region, off_n.data(), off_t.data(), &n_nodes,
                               &n_tris, why) != TT_OK)
         return fail(c, TT_ERR_INVALID_ARG, "tt_scene_assemble_objects: %s", why.c_str());
-    if (over_4gib(n_nodes, n_tris))
-        return fail(c, TT_ERR_INVALID_ARG, "scene validation failed: node or triangle array of 4 GiB or more (the trace kernel "
-                                           "addresses them with 32-bit offsets)");
+    if (over_4gib(n_nodes, n_tris)) return fail(c, TT_ERR_INVALID_ARG, "scene validation failed: %s", kOver4GiB);
     for (uint32_t i = 0; i < n_tlas; i++)
         if (tlas[i] < 0 || (uint32_t)tlas[i] >= n_mesh)
             return fail(c, TT_ERR_INVALID_ARG, "scene validation failed: TLASBVH8Indices entry %u (%d) out of range", i, tlas[i]);
     // every mesh record names one object by its (NodeOffset, TriOffset) pair of the layout, and a root that
     // object's own walk reached (so the subtree below it was validated against the object's counts)
     std::vector<uint8_t> used(n_objects, 0u);
-    std::vector<SceneHost::BlasKey> keys;
+    std::vector<tt_check::BlasKey> keys;
     for (uint32_t m = 0; m < n_mesh; m++) {
         const tt_mesh_data& r = md[m];
         if (r.NodeOffset < 0 || r.TriOffset < 0) return fail(c, TT_ERR_INVALID_ARG, "scene validation failed: negative mesh offsets");
@@ -654,10 +518,8 @@ tt_status tt_scene_assemble_objects(tt_ctx* c, const tt_object* const* objects, 
         if (root < off_n[i - 1] || root - off_n[i - 1] >= o->n_nodes || !o->walk.reach[root - off_n[i - 1]])
             return fail(c, TT_ERR_INVALID_ARG, "scene validation failed: mesh record %u: root %u is not a validated node of its "
                                                "object (nodes [%u, %u))", m, root, off_n[i - 1], off_n[i - 1] + o->n_nodes);
-        // (MaterialOffset + the object's largest MatDat against n_mat: check_scene computes that bound but
-        // enforces it nowhere, so neither does this path -- a scene upload accepts is accepted here)
         used[i - 1] = 1u;
-        keys.push_back(SceneHost::BlasKey{root, (uint32_t)r.NodeOffset, (uint32_t)r.TriOffset});
+        keys.push_back(tt_check::key_of(r));
     }
     std::sort(keys.begin(), keys.end());
     keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
@@ -672,17 +534,14 @@ tt_status tt_scene_assemble_objects(tt_ctx* c, const tt_object* const* objects, 
     std::vector<uint32_t> tags;
     bool any_invisible = false;
     derive_materials(mats, n_mat, h, tags, any_invisible);
-    // (h.matdat, upload's per-triangle MatDat copy for Invisible materials, stays empty: it feeds only the unused
-    // bound above)
     {
-        Validator v(h);
-        v.n_tl = tlas_region;
-        if (!v.walk(0, 0, 0, true)) return fail(c, TT_ERR_INVALID_ARG, "scene validation failed: TLAS: %s", v.why.c_str());
+        tt_check::SceneView s = view_of(h);
+        s.n_tl = tlas_region;
+        Validator v(s);
+        if (!v.walk_tlas()) return fail(c, TT_ERR_INVALID_ARG, "scene validation failed: TLAS: %s", v.why.c_str());
         h.blas_ok = keys;
-        h.tlas_nodes = v.tlas_visit;
+        tt_check::replace_tlas_reach(h.is_tlas_node, h.tlas_nodes, v.tlas_visit, n_nodes);
     }
-    h.is_tlas_node.assign(n_nodes, 0u);
-    for (uint32_t n : h.tlas_nodes) h.is_tlas_node[n] = 1u;
     h.is_blas_node.assign(n_nodes, 0u);
     for (uint32_t i = 0; i < n_objects; i++)
         if (used[i]) std::memcpy(h.is_blas_node.data() + off_n[i], objects[i]->walk.reach.data(), objects[i]->n_nodes);
@@ -875,12 +734,10 @@ tt_status tt_ctx_share_blas(tt_ctx* dst, tt_ctx* src, uint32_t n_tlas_nodes) {
     TT_HIP(dst, hipMemcpy(h.nodes.data(), src->scene.nodes.p, sizeof(tt_cwbvh_node) * n_tlas_nodes, hipMemcpyDeviceToHost));
     {
         std::lock_guard<std::recursive_mutex> lk(src->mu);
-        Validator v(h, src->host);
-        if (!v.walk(0, 0, 0, true))
+        Validator v(view_of(h, src->host));
+        if (!v.walk_tlas())
             return fail(dst, TT_ERR_INVALID_ARG, "tt_ctx_share_blas: the TLAS leaves [0, %u): %s", n_tlas_nodes, v.why.c_str());
-        h.is_tlas_node.assign(n_tlas_nodes, 0u);
-        h.tlas_nodes = v.tlas_visit;
-        for (uint32_t n : h.tlas_nodes) h.is_tlas_node[n] = 1u;
+        tt_check::replace_tlas_reach(h.is_tlas_node, h.tlas_nodes, v.tlas_visit, n_tlas_nodes);
     }
     const uint32_t n_tlas = (uint32_t)h.tlas.size(), n_mesh = (uint32_t)h.mesh.size();
     struct Fresh {  // dst's own TLAS-side buffers, adopted once nothing can fail any more
@@ -1413,19 +1270,14 @@ tt_status tt_scene_update_nodes(tt_ctx* c, uint32_t first, uint32_t count, const
             std::copy(saved.begin(), saved.end(), h.nodes.begin() + first);
             return fail(c, L ? TT_ERR_INVALID_ARG : TT_ERR_UNSUPPORTED, "%s", refuse);
         }
-        Validator v = L ? Validator(h, L->host) : Validator(h);
-        const bool ok = tlas_only ? v.walk(0, 0, 0, true) : v.run();
+        Validator v(view_of(c));
+        const bool ok = tlas_only ? v.walk_tlas() : v.run();
         if (!ok) {
             std::copy(saved.begin(), saved.end(), h.nodes.begin() + first);
             return fail(c, TT_ERR_INVALID_ARG, "scene validation failed after node update: %s", v.why.c_str());
         }
-        if (tlas_only) {
-            for (uint32_t n : h.tlas_nodes) h.is_tlas_node[n] = 0u;
-            h.tlas_nodes = v.tlas_visit;
-            for (uint32_t n : h.tlas_nodes) h.is_tlas_node[n] = 1u;
-        } else {
-            remember_validation(h, v);
-        }
+        if (tlas_only) tt_check::replace_tlas_reach(h.is_tlas_node, h.tlas_nodes, v.tlas_visit, 0);
+        else tt_check::remember_validation(h, v, h.nodes.size());
         if (first == 0) c->root_known = true;  // node 0 is the host's again
     }
     TT_HIP(c, hipSetDevice(c->device));
@@ -1455,7 +1307,7 @@ tt_status tt_scene_update_meshdata(tt_ctx* c, uint32_t first, uint32_t count, co
     // Only records whose BLAS reference (root, NodeOffset, TriOffset) changed need a check, and only
     // against the BLASes validated so far; a BLAS never seen is walked once and remembered. The
     // per-frame transform update (MeshDataBuffer.SetData, AssetManager.cs:1825) changes none.
-    std::vector<SceneHost::BlasKey> added;
+    std::vector<tt_check::BlasKey> added;
     for (uint32_t i = 0; i < count; i++) {
         const tt_mesh_data& r = md[i];
         const tt_mesh_data& o = h.mesh[first + i];
@@ -1464,13 +1316,12 @@ tt_status tt_scene_update_meshdata(tt_ctx* c, uint32_t first, uint32_t count, co
             continue;
         if (r.NodeOffset < 0 || r.TriOffset < 0)
             return fail(c, TT_ERR_INVALID_ARG, "scene validation failed after meshdata update: negative mesh offsets");
-        const SceneHost::BlasKey k{(uint32_t)(r.mesh_data_bvh_offsets & 0x7fffffff), (uint32_t)r.NodeOffset,
-                                   (uint32_t)r.TriOffset};
+        const tt_check::BlasKey k = tt_check::key_of(r);
         if (std::binary_search(h.blas_ok.begin(), h.blas_ok.end(), k) ||
             std::find(added.begin(), added.end(), k) != added.end())
             continue;
         std::lock_guard<std::recursive_mutex> lk(L ? L->mu : c->mu);
-        Validator v = L ? Validator(h, L->host) : Validator(h);
+        Validator v(view_of(c));
         if (!v.walk_mesh(r))
             return fail(c, TT_ERR_INVALID_ARG, "scene validation failed after meshdata update: %s", v.why.c_str());
         added.push_back(k);

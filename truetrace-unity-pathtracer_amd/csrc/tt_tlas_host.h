@@ -1,6 +1,7 @@
 // tt_tlas_host.h — the host-only half of a TLAS installation (tt_scene_update_tlas, tt_tlas_rebuild): the checks
 // that keep a malformed TLAS from reaching a kernel, the capacity of a scene's TLAS region, the shape of the one
-// install launch, and the host mirror's update. Plain C++ with no HIP in it, so a stand-alone program can run it
+// install launch, and the host mirror's update. Its walk is the shared one of tt_scene_check_host.h, with this
+// installation's bounds and messages. Plain C++ with no HIP in it, so a stand-alone program can run it
 // under the host sanitizers (tests/native/tlas_install_kat_main.cpp).
 #pragma once
 #include <cstdint>
@@ -9,6 +10,7 @@
 #include <vector>
 
 #include "../../include/truetrace_hip.h"
+#include "tt_scene_check_host.h"
 
 namespace tt_tlas {
 
@@ -17,58 +19,42 @@ struct Check {
     std::string why;
 };
 
-// Validator::walk(0, 0, 0, true) (tt_scene_api.hip) over the supplied nodes alone: IntersectBVH's index arithmetic
+// The shared walk (tt_scene_check_host.h) from node 0 over the supplied nodes alone: IntersectBVH's index arithmetic
 // at TLAS level (IntersectionKernels.compute:157-196). A child index must stay inside [0, n_nodes) -- the nodes
 // behind them are zeroed by the installation, never read from the caller -- and a leaf slot inside [0, n_idx).
-inline bool walk_tlas(const tt_cwbvh_node* nodes, uint32_t n_nodes, uint32_t n_idx, Check& k) {
-    k.visit.clear();
-    std::vector<uint8_t> seen(n_nodes, 0u);
-    std::vector<uint32_t> work{0u};
-    while (!work.empty()) {
-        const uint32_t ni = work.back();
-        work.pop_back();
-        if (ni >= n_nodes) {
-            k.why = "node index " + std::to_string(ni) + " out of range of the " + std::to_string(n_nodes) + " TLAS nodes";
-            return false;
-        }
-        if (seen[ni]) continue;
+struct TlasWalk {
+    const tt_cwbvh_node* nodes;
+    const uint32_t n_nodes, n_idx;
+    Check& k;
+    std::vector<uint8_t> seen = std::vector<uint8_t>(n_nodes, 0u);
+    bool refuse(const std::string& what) {
+        k.why = what;
+        return false;
+    }
+    TT_CHECK_INLINE bool node_in_range(uint64_t ni) {
+        return ni < n_nodes ||
+               refuse("node index " + std::to_string(ni) + " out of range of the " + std::to_string(n_nodes) + " TLAS nodes");
+    }
+    TT_CHECK_INLINE tt_check::Enter enter(uint32_t ni) {
+        if (!node_in_range(ni)) return tt_check::Enter::refused;
+        if (seen[ni]) return tt_check::Enter::seen;
         seen[ni] = 1u;
         k.visit.push_back(ni);
-        const tt_cwbvh_node& n = nodes[ni];
-        const uint32_t imask = n.e_imask >> 24;
-        for (int c = 0; c < 8; c++) {
-            const uint32_t meta = (n.meta[c >> 2] >> ((c & 3) * 8)) & 0xffu;
-            const uint32_t low5 = meta & 0x1fu, bits = (meta >> 5) & 7u;
-            if ((meta & 0x18u) == 0x18u) {
-                if (bits != 1u) {
-                    k.why = "inner meta with child bits != 1";
-                    return false;
-                }
-                const uint32_t slot = low5 - 24u;
-                const uint64_t child = (uint64_t)n.base_child + (uint32_t)__builtin_popcount(imask & ((1u << slot) - 1u));
-                if (child >= n_nodes) {
-                    k.why = "node index " + std::to_string(child) + " out of range of the " + std::to_string(n_nodes) + " TLAS nodes";
-                    return false;
-                }
-                work.push_back((uint32_t)child);
-            } else if (bits) {
-                const uint32_t top = low5 + (31u - (uint32_t)__builtin_clz(bits));
-                if (top >= 24u) {
-                    k.why = "leaf meta spills into the internal-child bits";
-                    return false;
-                }
-                for (uint32_t b = 0; b < 3; b++) {
-                    if (!((bits >> b) & 1u)) continue;
-                    const uint64_t t = (uint64_t)n.base_tri + low5 + b;
-                    if (t >= n_idx) {
-                        k.why = "TLAS leaf slot out of range";
-                        return false;
-                    }
-                }
-            }
-        }
+        return tt_check::Enter::fresh;
     }
-    return true;
+    const tt_cwbvh_node& node(uint32_t ni) const { return nodes[ni]; }
+    TT_CHECK_INLINE bool child(uint32_t, const tt_cwbvh_node& n, uint32_t rank, uint32_t& out) {
+        const uint64_t child = (uint64_t)n.base_child + rank;
+        out = (uint32_t)child;
+        return node_in_range(child);
+    }
+    TT_CHECK_INLINE bool leaf(uint32_t, uint64_t t) { return t < n_idx || refuse("TLAS leaf slot out of range"); }
+    bool bad_meta(uint32_t, const char* what) { return refuse(what); }
+};
+inline bool walk_tlas(const tt_cwbvh_node* nodes, uint32_t n_nodes, uint32_t n_idx, Check& k) {
+    k.visit.clear();
+    TlasWalk p{nodes, n_nodes, n_idx, k};
+    return tt_check::walk(0u, p);
 }
 
 // Everything tt_scene_update_tlas checks before anything is enqueued. n_idx_scene, n_mesh: the scene's current
@@ -156,16 +142,12 @@ inline void apply_mirror(const Plan& p, const tt_cwbvh_node* nodes, const int32_
                          std::vector<uint32_t>& tlas_nodes) {
     if (slot) {
         mirror.assign(nodes, nodes + p.n_nodes);
-        is_tlas_node.assign(p.n_nodes, 0u);
     } else {
         std::memcpy(mirror.data(), nodes, (size_t)p.n_nodes * sizeof(tt_cwbvh_node));
         if (p.n_clear) std::memset(mirror.data() + p.n_nodes, 0, (size_t)p.n_clear * sizeof(tt_cwbvh_node));
-        for (uint32_t n : tlas_nodes)
-            if (n < is_tlas_node.size()) is_tlas_node[n] = 0u;
     }
     tlas.assign(idx, idx + p.n_idx);
-    tlas_nodes = k.visit;
-    for (uint32_t n : tlas_nodes) is_tlas_node[n] = 1u;
+    tt_check::replace_tlas_reach(is_tlas_node, tlas_nodes, k.visit, slot ? p.n_nodes : 0u);
 }
 
 }  // namespace tt_tlas
