@@ -31,9 +31,12 @@ d_obj / |d_obj|), robust for |c| > 1e-5 and marginal otherwise; or at bounce 0 w
 Any-hit, range (0, |t_ray|), or (0, t_ray) in the visibility-check mode (empty for t_ray <= 0): rejected for
 IsBackground, ShadowCaster or specTrans == 1. A material index outside the table reads a zero material.
 
-Cutout materials are out of scope: the alpha test needs a float64 texture sampler, and the scenes this
-reference is used with hold none. Glass tints are not computed either (they depend on which nodes a
-traversal reaches); ``any_hit`` only says for which rays no glass triangle can have tinted.
+Cutout materials and glass tints are the business of materials.py, the float64 texture-space model: it hands
+``closest`` and ``any_hit`` a material hook, ``material(m, lo, hi, B) -> (reject, unsure)``, two boolean arrays
+of the block's shape. A rejected pair is OUT whatever its geometry (the alpha test rejects robustly), an unsure
+pair that is not rejected otherwise is MARGINAL (the alpha test could turn on a float32 rounding). Without a
+hook nothing changes: Cutout materials count as opaque, and ``any_hit`` only says for which rays no glass
+triangle can have tinted (the tints depend on which nodes a traversal reaches; materials.py bounds them).
 """
 from __future__ import annotations
 
@@ -187,9 +190,9 @@ class Closest:
     cond_v: np.ndarray
 
 
-def closest(g: Geometry, origins, dirs, far, flags=0, bounce=0, honour_invisible=True) -> Closest:
+def closest(g: Geometry, origins, dirs, far, flags=0, bounce=0, honour_invisible=True, material=None) -> Closest:
     """Closest hit per ray. honour_invisible=False leaves the Invisible test out (a deliberately wrong
-    reference, for the tests that prove the comparison can fail)."""
+    reference, for the tests that prove the comparison can fail). material: the hook of the module docstring."""
     o, d = np.asarray(origins, np.float64), np.asarray(dirs, np.float64)
     n = len(o)
     best, second, marg = np.full(n, np.inf), np.full(n, np.inf), np.full(n, np.inf)
@@ -201,6 +204,10 @@ def closest(g: Geometry, origins, dirs, far, flags=0, bounce=0, honour_invisible
         glass, tag = g._material(m, lo, hi)
         reject = np.zeros(B.t.shape, bool)
         unsure = np.zeros(B.t.shape, bool)
+        if material is not None:
+            mr, mu = material(m, lo, hi, B)
+            reject |= mr
+            unsure |= mu
         if flags & tthip.TT_TRACE_IGNORE_GLASS:
             reject |= glass[None, :]
         if bounce == 0 and honour_invisible:
@@ -208,7 +215,8 @@ def closest(g: Geometry, origins, dirs, far, flags=0, bounce=0, honour_invisible
         if (flags & tthip.TT_TRACE_IGNORE_BACKFACING) and bounce == 0:
             with np.errstate(invalid="ignore"):
                 reject |= ~glass[None, :] & (B.c < -C_MIN)
-                unsure = ~glass[None, :] & ~(np.abs(B.c) > C_MIN) & ~reject
+                unsure = unsure | (~glass[None, :] & ~(np.abs(B.c) > C_MIN))
+        unsure = unsure & ~reject
         inside, marginal = _classify(B, t_end, ~reject & ~unsure, reject)
         with np.errstate(invalid="ignore"):
             exact |= ((B.u >= 0) & (B.u <= 1) & (B.v >= 0) & (B.u + B.v <= 1) & (B.t > 0) & (B.t < far) & ~reject).any(axis=1)
@@ -267,9 +275,9 @@ class AnyHit:
     glass_clear: np.ndarray  # every glass triangle is robustly missed in u, v alone: nothing can have tinted
 
 
-def any_hit(g: Geometry, origins, dirs, t_ray, visibility_check=False, honour_tags=True) -> AnyHit:
+def any_hit(g: Geometry, origins, dirs, t_ray, visibility_check=False, honour_tags=True, material=None) -> AnyHit:
     """Occlusion per shadow ray. honour_tags=False leaves the IsBackground / ShadowCaster skips out (a
-    deliberately wrong reference)."""
+    deliberately wrong reference). material: the hook of the module docstring."""
     o, d = np.asarray(origins, np.float64), np.asarray(dirs, np.float64)
     t_ray = np.asarray(t_ray, np.float64)
     n = len(o)
@@ -282,7 +290,12 @@ def any_hit(g: Geometry, origins, dirs, t_ray, visibility_check=False, honour_ta
         if honour_tags:
             reject |= (tag & skip) != 0
         reject = np.broadcast_to(reject[None, :], B.t.shape)
-        inside, marginal = _classify(B, t_end, ~reject, reject)
+        accept = ~reject
+        if material is not None:
+            mr, mu = material(m, lo, hi, B)
+            reject = reject | mr
+            accept = ~reject & ~mu
+        inside, marginal = _classify(B, t_end, accept, reject)
         occluded |= inside.any(axis=1)
         marginal_any |= marginal.any(axis=1)
         clear &= (_uv_out(B) | ~glass[None, :]).all(axis=1)

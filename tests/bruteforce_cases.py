@@ -227,6 +227,7 @@ class Report:
     mismatches: int
     failures: list
     text: str
+    tint: tuple = None  # compare_any_hit with a tint model: (largest row ratio, largest Direct ratio, rays resolved with O)
 
     def check(self):
         print(self.text)
@@ -308,7 +309,7 @@ def reference_any_hit(g, srays, visibility_check=False, **kw):
 
 
 def compare_any_hit(ref: BF.AnyHit, before, after, vis, col, nee, bounce, visibility_check=False, status=None,
-                    caps=True) -> Report:
+                    caps=True, tint=None, tint_check=None) -> Report:
     """What an any-hit call left (`after`: the rays in place, vis / col / nee from shadow_outputs) against the
     reference, on robust rays; `before` are the rays as handed in, one per pixel. status: the oracle's
     counts.status, or None.
@@ -321,7 +322,13 @@ def compare_any_hit(ref: BF.AnyHit, before, after, vis, col, nee, bounce, visibi
     coordinate magnitude of the segment's end points o and p: fl(o + fl(d |t|)) is off by at most
     2^-24 (|d |t|| + |p|) <= 2^-24 (|o| + 2 |p|) <= 3 * 2^-24 * M per component, plus one for slack; it stays
     untouched for occluded rays and at bounce 1.
-    Visibility-check mode: rows are (1, 1, 1, 1) or (0, 0, 0, 0) and nothing else is written."""
+    Visibility-check mode: rows are (1, 1, 1, 1) or (0, 0, 0, 0) and nothing else is written.
+
+    tint, tint_check (a materials.Tint and materials.tint_check, handed in by the caller; the default mode only):
+    the visibility rows of robustly visible rays must also satisfy the subset rule of tint_check, and at bounce 0 the Direct of a visible ray with t >= 0 whose
+    row is not all ones lies within two roundings (the product and the sum, all terms positive) of 0.5 +
+    illumination * row, row the float32 row that was written: |Direct - x| <= 2 * 2^-24 * x. The report's
+    `tint` holds (largest row ratio, largest Direct ratio, rays with O non-empty the rule resolves)."""
     n = len(before)
     r = ref.robust
     pix = before["PixelIndex"].astype(np.int64)
@@ -329,6 +336,7 @@ def compare_any_hit(ref: BF.AnyHit, before, after, vis, col, nee, bounce, visibi
     t_in, t_out = before["t"], after["t"]
     fails, text = _caps(r, ref.occluded, "occluded", "visible", caps)
     occ, see = r & ref.occluded, r & ~ref.occluded
+    extra = None
 
     def need(cond, where, what):
         bad = np.nonzero(where & ~cond)[0]
@@ -362,11 +370,26 @@ def compare_any_hit(ref: BF.AnyHit, before, after, vis, col, nee, bounce, visibi
             need((got == NEE0).all(1), occ, "NEEPosA of an occluded ray was written")
         else:
             need((got == NEE0).all(1), np.ones(n, bool), "NEEPosA was written at bounce 1")
+        if tint is not None:
+            bad, row_ratio, resolved, _ = tint_check(tint, vis[:, :3], see)
+            mism += len(bad)
+            if bad:
+                fails.append(f"{len(bad)} robust visible rays: the visibility row is no product of the tints the ray "
+                             f"must and may cross, first ray {bad[0]} (row {vis[bad[0], :3]}, |R| {tint.r_n[bad[0]]}, "
+                             f"|O| {len(tint.o_tints[bad[0]])})")
+            x = DIRECT0 + il.astype(np.float64) * vis[:, :3].astype(np.float64)
+            tinted = see & (t_in >= 0) & ~one_row if bounce == 0 else np.zeros(n, bool)
+            dr = (np.abs(direct.astype(np.float64) - x) / (2 * BF.U24 * x)).max(1)
+            direct_ratio = float(dr[tinted].max()) if tinted.any() else 0.0
+            mism += need(dr <= 1, tinted, "Direct is not within two roundings of 0.5 + illumination * row")
+            extra = (row_ratio, direct_ratio, resolved)
+            text += (f", largest tint ratio {row_ratio:.3g}, largest Direct ratio {direct_ratio:.3g} over "
+                     f"{int(tinted.sum())} tinted rays, {resolved} rays resolved with O non-empty")
     if status is not None:
         mism += need(status == 4, occ, "occluded but counts.status != 4")
         mism += need(status == 0, see, "visible but counts.status != 0")
     text += f", {int((see & ~ref.glass_clear).sum())} visible rays may cross glass"
-    return Report(mism, fails, text)
+    return Report(mism, fails, text, extra)
 
 
 # ------------------------------------------------------------------ refits
