@@ -8,6 +8,7 @@ the reordered dequeue skipped would show. Covered: the full-frame 8x8 tile swizz
 lists; ragged counts (the partial last chunk must stay last); counts below one chunk per segment; a
 screen-size change (costs dropped); the material-check kernel form; _PrimaryTriangleInfo at bounce 0
 and the GlobalColors-gated form at bounce 1; C2 at 1080p (primary + its compacted bounce-1 rays).
+What the order IS -- the sort, the recorded costs, the ping-pong -- is pinned in tests/test_gpu_order_pin.py.
 
 tt_trace_closest_hits: the compact hit-record stream the multi-GPU gather sends."""
 import numpy as np

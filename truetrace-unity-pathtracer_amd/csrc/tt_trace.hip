@@ -446,9 +446,10 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                 if (STATS) c_hits += hit ? 1u : 0u;
                 if (ORD) record_chunk_cost(A, swizzle, w.ray_index, w.Reps);
             };
-            auto exhaust_wide = [&](const WideState& w) {
+            auto exhaust_wide = [&](const WideState& w, bool overflow) {
                 keep_record(A, w.ray_index);
-                if (ORD) record_chunk_cost(A, swizzle, w.ray_index, w.Reps);
+                // (an overflowed ray records no cost, as in the narrow loop: only the Reps bound does)
+                if (ORD && !overflow) record_chunk_cost(A, swizzle, w.ray_index, w.Reps);
             };
             wide_phase<STATS, MATCHECK, 2, LEAF>(A, st, s_stack, spill, spill_stride, nodes, tris, lane,
                                            Counters{c_nodes, c_tris, c_blas, c_acc, c_hits, c_reps, c_ovf},

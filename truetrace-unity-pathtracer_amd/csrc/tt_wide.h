@@ -204,8 +204,8 @@ __device__ __forceinline__ uint32_t node_intersect_part(const uint4 n0, const ui
 
 // The drain loop for groups of G lanes; regroups into 2G-lane groups when the live rays fit and
 // returns when every ray of the wave has finished. `finish(st)` writes a finished ray's records,
-// `exhaust(st)` sees a ray that ends without a record (the Reps bound or a stack overflow: the
-// reference writes nothing for it); both are called on the group's first lane only.
+// `exhaust(st, overflow)` sees a ray that ends without a record (the Reps bound, or with overflow
+// set a stack overflow: the reference writes nothing for it); both are called on the group's first lane only.
 // LEAF: every ray is inside the one instance's BLAS for good (st.NodeOffset / TriOffset / MatOffset hold the
 // instance's wave-uniform values): no TLAS leaf -> BLAS switch and no BLAS exit.
 template <bool STATS, bool MATCHECK, int G, int LEAF, class Finish, class Exhaust>
@@ -235,7 +235,7 @@ __device__ void wide_phase(const TraceArgs& A, WideState& st, uint2 (*s_stack)[T
             if (st.Reps >= TT_MAX_REPS) {
                 st.active = false;  // loop bound hit: the reference writes nothing
                 if (STATS && sub == 0u) C.reps++;
-                if (sub == 0u) exhaust(st);
+                if (sub == 0u) exhaust(st, false);
             } else if (st.cg.y & 0xff000000u) {  // IntersectionKernels.compute:157-187
                 const uint32_t child = take_child(st.cg, st.oct);
                 bool ok = true;
@@ -255,7 +255,7 @@ __device__ void wide_phase(const TraceArgs& A, WideState& st, uint2 (*s_stack)[T
                     if (sub == 0u) {
                         if (STATS) C.ovf++;
                         TT_REPORT_OVERFLOW(A);
-                        exhaust(st);
+                        exhaust(st, true);
                     }
                 }
             } else {  // :188-191
@@ -282,7 +282,7 @@ __device__ void wide_phase(const TraceArgs& A, WideState& st, uint2 (*s_stack)[T
                     if (sub == 0u) {
                         if (STATS) C.ovf++;
                         TT_REPORT_OVERFLOW(A);
-                        exhaust(st);
+                        exhaust(st, true);
                     }
                 }
                 st.tg.y = 0u;
