@@ -618,7 +618,9 @@ static uint32_t packRGBE(const float v[3]) { /* :479-496 */
     if (max_abs == 0.0f) return 0u;
     int e;
     (void)frexpf(max_abs, &e);
-    const float exponent = (float)(e - 1); /* floor(log2(max_abs)) */
+    /* floor(log2(max_abs)), exact; log2(inf) is inf (frexp leaves e unspecified there): the field clamps to 31, the
+     * scale is pow(2, -inf) * 256 = 0, inf * 0 is NaN and min(511, NaN) is 511 */
+    const float exponent = max_abs == INFINITY ? INFINITY : (float)(e - 1);
     uint32_t result = d3d_ftou(clampf3(exponent + 20.0f, 0.0f, 31.0f)) << 27;
     const float scale = p_exp2f(-exponent) * 256.0f; /* pow(2, -exponent) * 256 */
     uint32_t vu[3];

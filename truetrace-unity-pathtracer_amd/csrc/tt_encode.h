@@ -80,7 +80,9 @@ __device__ __forceinline__ uint32_t packRGBE(float r, float g, float b) {
     if (max_abs == 0.0f) return 0u;
     int e;
     (void)frexpf(max_abs, &e);
-    const float exponent = (float)(e - 1);  // floor(log2(max_abs)), exact
+    // floor(log2(max_abs)), exact; log2(inf) is inf (frexp leaves e unspecified there): the field clamps to 31, the
+    // scale is pow(2, -inf) * 256 = 0, inf * 0 is NaN and min(511, NaN) is 511
+    const float exponent = max_abs == __builtin_inff() ? __builtin_inff() : (float)(e - 1);
     uint32_t result = ftou(clampf(exponent + 20.0f, 0.0f, 31.0f)) << 27;
     const float scale = exp2f_pinned(-exponent) * 256.0f;
     uint32_t vu[3];
