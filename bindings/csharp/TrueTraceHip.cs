@@ -24,6 +24,7 @@ namespace TrueTrace.Hip
         IgnoreBackfacing = 1u << 6,  // IgnoreBackfacing (IntersectionKernels.compute:45-47)
         AdaptiveOrder = 1u << 7,     // dequeue the previous launch's costliest 8x8 tiles first (same results)
         TerrainBounce = 1u << 8,     // tt_enqueue_diffuse_bounce(_indirect): terrain hits bounce off the terrain
+        NeeNegativeT = 1u << 9,      // tt_emit_nee(_indirect): every written t negated (PrimaryNEERay / Indirect form)
         RadianceCache = 1u << 7,     // tt_trace_shadow_ex: the RadianceCache define (GlobalDefines.cginc:15)
         VisibilityCheck = 1u << 8    // tt_trace_shadow_ex: VisabilityCheckCompute (CommonData.cginc:710-819)
     }
@@ -284,6 +285,18 @@ namespace TrueTrace.Hip
             IntPtr globalRays, int framesAccumulated, int maxBounce, out uint nNext);
         [DllImport(Lib)] public static extern TTStatus tt_enqueue_diffuse_bounce_indirect(IntPtr ctx, ref TTTraceParams p,
             IntPtr nRaysDev, IntPtr globalRays, int framesAccumulated, int maxBounce, IntPtr nNextDev);
+        // Lights: LightNodes (40 B) / LightTriangles (40 B) / _LightMeshes (28 B) of the scene, and the NEE emit that
+        // turns traced hits into ShadowRayData toward them (samples: 48-byte tt_light_sample per traced ray, nullable)
+        [DllImport(Lib)] public static extern TTStatus tt_lights_validate(IntPtr nodes, uint nNodes, IntPtr tris, uint nTris,
+            IntPtr meshes, uint nMeshes, IntPtr meshData, uint nMesh, uint nSceneTris, byte[] why, uint whyLen);
+        [DllImport(Lib)] public static extern TTStatus tt_scene_upload_lights(IntPtr ctx, IntPtr nodes, uint nNodes,
+            IntPtr tris, uint nTris, IntPtr meshes, uint nMeshes);
+        [DllImport(Lib)] public static extern TTStatus tt_scene_update_light_nodes(IntPtr ctx, uint first, uint count,
+            IntPtr nodes);
+        [DllImport(Lib)] public static extern TTStatus tt_emit_nee(IntPtr ctx, ref TTTraceParams p, IntPtr globalRays,
+            int framesAccumulated, int maxBounce, IntPtr samples, IntPtr shadowRays, out uint nShadow);
+        [DllImport(Lib)] public static extern TTStatus tt_emit_nee_indirect(IntPtr ctx, ref TTTraceParams p, IntPtr nRaysDev,
+            IntPtr globalRays, int framesAccumulated, int maxBounce, IntPtr samples, IntPtr shadowRays, IntPtr nShadowDev);
         // GetTriangleNormal per hit: float[6] (shading xyz, geometric xyz) per ray
         [DllImport(Lib)] public static extern TTStatus tt_resolve_normals(IntPtr ctx, ref TTTraceParams p, IntPtr globalRays,
             IntPtr normals6);

@@ -1050,6 +1050,128 @@ tt_status tt_enqueue_diffuse_bounce_indirect(tt_ctx* ctx, const tt_trace_params*
                                              tt_ray_data* global_rays, int32_t frames_accumulated,
                                              int32_t max_bounce, uint32_t* n_next_dev);
 
+/* --------------------------------- lights: the light BVH and next event estimation */
+/* LightBVHData, 40 B (CommonData.cginc:987-994, CommonVars.cs:294-302). w: the cone axis, octahedral 16:16;
+ * cosTheta_oe: floor(32767 (cosTheta_o + 1) / 2) in the low half, the same of cosTheta_e in the high half;
+ * left >= 0: the even index of the first of two adjacent children (relative to the tree's first node);
+ * left < 0: a leaf holding -(left + 1) (a _LightMeshes row in the TLAS part, else a light triangle relative
+ * to the mesh's StartIndex). */
+typedef struct tt_light_node {
+    float BBMax[3];
+    float BBMin[3];
+    uint32_t w;
+    float phi;
+    uint32_t cosTheta_oe;
+    int32_t left;
+} tt_light_node;
+TT_STATIC_ASSERT(sizeof(tt_light_node) == 40, "LightBVHData is 40 bytes");
+
+/* LightTriData, 40 B (CommonData.cginc:297-302): the triangle in its mesh's space; TriTarget is its index
+ * among the mesh's triangles (_MeshData.TriOffset is added on the device). */
+typedef struct tt_light_tri {
+    float pos0[3];
+    float posedge1[3];
+    float posedge2[3];
+    uint32_t TriTarget;
+} tt_light_tri;
+TT_STATIC_ASSERT(sizeof(tt_light_tri) == 40, "LightTriData is 40 bytes");
+
+/* LightMeshData, 28 B (CommonData.cginc:308-314): [StartIndex, IndexEnd) are the mesh's rows of
+ * LightTriangles, LockedMeshIndex its _MeshData record. */
+typedef struct tt_light_mesh {
+    float Center[3];
+    int32_t StartIndex;
+    int32_t IndexEnd;
+    int32_t MatOffset;
+    int32_t LockedMeshIndex;
+} tt_light_mesh;
+TT_STATIC_ASSERT(sizeof(tt_light_mesh) == 28, "LightMeshData is 28 bytes");
+
+/* Hard loop bound of SampleLightBVH: while (Reps < 322) (CommonData.cginc:1132). */
+#define TT_LIGHT_MAX_REPS 322
+
+/* What tt_emit_nee reports per traced ray, 48 B. A ray that missed, a terrain record and a ray beyond
+ * far_plane get the "-1 record": light_tri = mesh_index = agg_tri = -1 and zeros. A hit whose descent ends
+ * without a light (both importances zero) has light_tri = agg_tri = -1, the mesh_index reached so far
+ * (-1 in the TLAS part), steps and weight as they stood, and zeros. */
+typedef struct tt_light_sample {
+    int32_t light_tri;   /* index into LightTriangles, or -1                                   */
+    int32_t mesh_index;  /* the _MeshData index of the light's instance (LockedMeshIndex)      */
+    int32_t agg_tri;     /* TriTarget + TriOffset                                              */
+    int32_t steps;       /* Reps when SampleLightBVH returned                                  */
+    float weight;        /* lightWeight after SampleLightBVH (from selectionoptions = 1)       */
+    float area;          /* world area (RayTracingShader.compute:405-407)                      */
+    float position[3];   /* world LightPosition (:408)                                         */
+    float normal[3];     /* world LightNorm (:409)                                             */
+} tt_light_sample;
+TT_STATIC_ASSERT(sizeof(tt_light_sample) == 48, "tt_light_sample is 48 bytes");
+
+/* tt_trace_params.flags of tt_emit_nee(_indirect), beyond TT_TRACE_DEVICE_PTRS / TT_TRACE_ASYNC: every
+ * written t is negated (the PrimaryNEERay / Indirect form of kernel_shadow's accumulation). The reference
+ * derives the sign from the radiance-cache path state (:465-474), which is the shading side. */
+enum { TT_NEE_NEGATIVE_T = 1u << 9 };
+
+/* The structural check tt_scene_upload_lights runs (host only, no device): everything SampleLightBVH's index
+ * arithmetic (CommonData.cginc:1126-1166) and the caller (:1913-1920) can reach is in range, and the descent
+ * ends. meshdata / n_mesh are the scene's _MeshData, n_scene_tris its triangle count. Refused, with the
+ * offending index in why (nullable): an interior left that is odd, out of range or not greater than its
+ * node's own index (children behind their parent: no cycle, so the descent is finite); a TLAS leaf whose
+ * light mesh is >= n_meshes; a LockedMeshIndex outside _MeshData; a LightNodeOffset that is odd, below
+ * 2 * n_meshes or past the nodes; a mesh-tree leaf outside [StartIndex, IndexEnd); a TriTarget outside its
+ * mesh's triangles; a descent longer than TT_LIGHT_MAX_REPS steps. The TLAS part is nodes [0, 2 * n_meshes). */
+tt_status tt_lights_validate(const tt_light_node* nodes, uint32_t n_nodes, const tt_light_tri* tris, uint32_t n_tris,
+                             const tt_light_mesh* meshes, uint32_t n_meshes, const tt_mesh_data* meshdata,
+                             uint32_t n_mesh, uint32_t n_scene_tris, char* why, uint32_t why_len);
+/* LightNodes, LightTriangles and _LightMeshes of the context's scene (AssetManager.cs:1100-1204, :1705),
+ * validated with tt_lights_validate against the scene's _MeshData. They belong to the scene: a
+ * tt_ctx_share_scene borrower sees them, and tt_scene_upload / tt_scene_assemble_objects drop them.
+ * TT_ERR_NO_SCENE without a scene; a borrower and a lender with borrowers refuse, as for tt_scene_upload. */
+tt_status tt_scene_upload_lights(tt_ctx* ctx, const tt_light_node* nodes, uint32_t n_nodes, const tt_light_tri* tris,
+                                 uint32_t n_tris, const tt_light_mesh* meshes, uint32_t n_meshes);
+/* Rewrites LightNodes[first, first + count) (a host that moved a light mesh rebuilds the TLAS part,
+ * AssetManager.cs:1681-1707); the whole set is validated again before anything is copied. Ordered against the
+ * borrowers' launches like tt_scene_update_nodes. */
+tt_status tt_scene_update_light_nodes(tt_ctx* ctx, uint32_t first, uint32_t count, const tt_light_node* nodes);
+
+/* Next event estimation toward the scene's emissive triangles for the rays traced at p->bounce: the geometric
+ * subset of kernel_shade's NEE block (RayTracingShader.compute:328-344, :391-409, :418-479) for triangle
+ * lights, as the enqueue is the subset that produces the next ray. Per hit (t < far_plane, a triangle record):
+ *   pos, the shading normal norm (octahedral round trip), its flip and ray.origin = USGNorm * 1e-4 + pos are
+ *     exactly tt_enqueue_diffuse_bounce's;
+ *   SelectedLightGroup = 0 (LightMeshCount != 0, no unity lights, no sky), so RunningWeight starts at 1;
+ *   the light is SampleLightBVH(pos, norm) (CommonData.cginc:1126-1166, Importance :1007-1043): a stochastic
+ *     descent of the two-level light BVH with random(264 + Reps, pixel).x, bounded by TT_LIGHT_MAX_REPS;
+ *   FinalUV = sample_triangle(random(79, pixel)) (:824-833), LightPosition, area and LightNorm in world space
+ *     through inverse(W2L) of the light's instance (:401-409; AreaOfTriangle is Heron's formula);
+ *   to_light, distance_to_light and SurfaceCos = dot(to_light, norm) (:419-426): a ray needs SurfaceCos > 0.
+ * The BSDF is a diffuse stand-in, NOT the reference's Disney BSDF: bsdf_value = bsdf_pdf = SurfaceCos / pi, a ray
+ * needs bsdf_pdf > 0.0001f; no Russian roulette (UseRussianRoulette off); NEE_pdf per :445; illumination =
+ * (bsdf_value / NEE_pdf) * power_heuristic(NEE_pdf, bsdf_pdf) in all three channels (throughput 1, radiance 1).
+ * Material emission and the emission atlas (CommonData.cginc:1921-1960) are not restated. The record written is
+ * {ray.origin, asfloat(packRGBE(bsdf_value.xxx)), to_light, distance_to_light - 0.01f (negated with
+ * TT_NEE_NEGATIVE_T), illumination, PixelIndex}. Survivors are compacted in source order with a stable scan
+ * (tile ballot / LDS prefix / decoupled look-back, as the enqueue), so the output is deterministic byte for byte.
+ * PixelIndex and tt_ctx_set_frame_pixels behave as in the enqueue. On a context with terrains a terrain record
+ * emits nothing.
+ *   samples      nullable: one tt_light_sample per traced ray (p->n_rays rows);
+ *   shadow_rays  nullable: room for p->n_rays rows; rows past the survivor count are not touched;
+ *   n_shadow     the survivor count. With TT_TRACE_ASYNC (device pointers) the call returns without waiting
+ *                and n_shadow is not written (it may be NULL).
+ * Numerics: the header's contract; pow(x, 2) and packRGBE are the pinned forms of the shadow kernel; inverse()
+ * is the cofactor expansion by 3x3 minors, each a * (e i - f h) - b * (d i - f g) + c * (d h - e g), times
+ * 1 / det. Results are bit-identical to tt_emit_nee_host (truetrace_scene.h).
+ * TT_ERR_NO_SCENE without a scene or without lights; TT_ERR_UNSUPPORTED on a frame slot (tt_ctx_share_blas):
+ * frame slots and groups do not carry lights. */
+tt_status tt_emit_nee(tt_ctx* ctx, const tt_trace_params* p, const tt_ray_data* global_rays,
+                      int32_t frames_accumulated, int32_t max_bounce, tt_light_sample* samples,
+                      tt_shadow_ray* shadow_rays, uint32_t* n_shadow);
+/* The same with device-resident counts: traces min(*n_rays_dev, p->n_rays) rays (n_rays_dev nullable:
+ * p->n_rays) and writes the survivor count to the device uint32 n_shadow_dev (BufferSizes[CurBounce].shadow_rays),
+ * without synchronizing, so it chains into tt_trace_shadow_ex_indirect. Requires TT_TRACE_DEVICE_PTRS. */
+tt_status tt_emit_nee_indirect(tt_ctx* ctx, const tt_trace_params* p, const uint32_t* n_rays_dev,
+                               const tt_ray_data* global_rays, int32_t frames_accumulated, int32_t max_bounce,
+                               tt_light_sample* samples, tt_shadow_ray* shadow_rays, uint32_t* n_shadow_dev);
+
 /* ------------------------------- multi-GPU tile-sharded frames */
 /* The reference traces a frame with one dispatch per bounce on one GPU
  * (RayTracingMaster.cs:954-1007: Generate, then kernel_trace / kernel_shade per bounce). A group

@@ -185,6 +185,79 @@ tt_status tt_terrain_bounce_host(const tt_terrain* terrains, uint32_t n, const u
                                  int32_t frames, int32_t max_bounce, uint32_t frame_pixels, tt_ray_data* out_rays,
                                  int32_t* survives);
 
+/* ------------------------------------------------------------------ lights (host/tt_lights.cpp)
+ * The host side of the light BVH: LightBVHBuilder.cs (both constructors), the light-triangle gather
+ * (ParentObject.cs:1061-1075, :733-739) and the buffer layout of AssetManager.cs:998-1040, :1100-1204,
+ * :1681-1707, restated. The reference sorts with System.Array.Sort (unstable) and ships no serialized light
+ * trees, so tree topology is not pinned to it: these builders use a STABLE sort (ties keep index order) and are
+ * deterministic. acos / asin / sin / cos run in double and round to float, as the C# does. */
+/* LightBounds (CommonVars.cs:267-285): a box, a normal cone (axis w, half-angle acos(cosTheta_o)), the emission
+ * falloff cosTheta_e, the power phi and the light count below. */
+typedef struct tt_light_bounds {
+    float BBMax[3];
+    float BBMin[3];
+    float w[3];
+    float phi;
+    float cosTheta_o;
+    float cosTheta_e;
+    int32_t LightCount;
+    float Pad1;
+} tt_light_bounds;
+
+/* LightTriData of the triangles `targets` (n_targets indices < n) of a mesh's 88-byte records: pos0 / posedge1 /
+ * posedge2 copied, TriTarget = the index. out_normals (n_targets x 3): normals when given, else the normalized
+ * mean of the record's three decoded octahedral normals -- this library's stand-in for ParentObject.cs:1068,
+ * which averages the source mesh's vertex normals before they are packed. */
+tt_status tt_light_tris_from_mesh(const tt_cuda_triangle* tris, uint32_t n, const uint32_t* targets, uint32_t n_targets,
+                                  const float* normals, tt_light_tri* out_tris, float* out_normals);
+/* LightBVHBuilder(List<LightTriData>, List<Vector3>, phi) (LightBVHBuilder.cs:271-342): per triangle a box
+ * (Validate 0.0001), the cone (-normal, cosTheta_o 1), phi 0.1, cosTheta_e = (float)cos(3.14159f / 2); the
+ * presort by box centre per axis, partition_sah with EvaluateCost, the UnionCone rules, the packing of
+ * :324-338. nodes holds 2 n records (node 1 is never referenced); root (nullable) receives ParentBound.
+ * A split whose every cost is NaN (a zero box extent makes Kr infinite) falls back to the middle of axis 0;
+ * the reference leaves split.index at -1 there. */
+tt_status tt_light_bvh_build_mesh(const tt_light_tri* tris, const float* normals, uint32_t n, tt_light_node* nodes,
+                                  tt_light_bounds* root);
+/* LightBVHBuilder(LightBounds[]) (:345-409) over per-light-mesh bounds; leaves hold the bound's index. */
+tt_status tt_light_bvh_build_tlas(const tt_light_bounds* bounds, uint32_t n, tt_light_node* nodes);
+/* A mesh tree's root bound under the instance's localToWorld (column-major), AssetManager.cs:1686-1704: the box
+ * about the transformed centre, the axis (Mat * w).normalized. The half extent is transformed with |Mat|, so
+ * that the box encloses the transformed box under any rotation or mirroring; the reference applies Mat itself
+ * (transform_direction), which is the same for the positive diagonal matrices it is exact for. */
+tt_status tt_light_bounds_transform(const tt_light_bounds* root, const float* local_to_world, tt_light_bounds* out);
+
+typedef struct tt_light_parent {  /* one mesh with emissive triangles: one light tree */
+    const tt_light_tri* tris;
+    const float* normals;         /* n_tris x 3 */
+    uint32_t n_tris;
+} tt_light_parent;
+typedef struct tt_light_instance {  /* one light mesh: a parent's tree under a transform */
+    uint32_t parent;
+    int32_t mesh_index;             /* its _MeshData record (LockedMeshIndex) */
+    float local_to_world[16];       /* column-major */
+} tt_light_instance;
+/* Lays LightNodes / LightTriangles / _LightMeshes out as the reference does: the TLAS over the instances in
+ * nodes [0, 2 n_instances), each parent's tree behind it at an even offset, which becomes LightNodeOffset of
+ * the _MeshData record of every instance of that parent (instances share their parent's tree and its rows of
+ * LightTriangles); LightTriCount = the parent's triangle count. _LightMeshes row i = instance i:
+ * StartIndex / IndexEnd its parent's rows, LockedMeshIndex, MatOffset = the record's MaterialOffset, Center the
+ * centre of its world box. nodes_out holds 2 n_instances + 2 sum(n_tris) records, tris_out sum(n_tris),
+ * meshes_out n_instances; *n_nodes / *n_tris receive the counts. meshdata is updated in place. */
+tt_status tt_lights_assemble(const tt_light_parent* parents, uint32_t n_parents, const tt_light_instance* instances,
+                             uint32_t n_instances, tt_mesh_data* meshdata, uint32_t n_mesh, tt_light_node* nodes_out,
+                             uint32_t* n_nodes, tt_light_tri* tris_out, uint32_t* n_tris, tt_light_mesh* meshes_out);
+/* The scalar host reference of tt_emit_nee (truetrace_hip.h): one ray at a time, float32, the same outputs bit
+ * for bit. global_rays is the array the kernel reads (the bounce half p selects); frame_pixels as
+ * tt_ctx_set_frame_pixels; terrains != 0: the scene has a terrain set (terrain records emit nothing).
+ * p->flags: TT_NEE_NEGATIVE_T. samples / shadow_rays nullable. The lights are checked with the rules of
+ * tt_lights_validate first (TT_ERR_INVALID_ARG). */
+tt_status tt_emit_nee_host(const tt_light_node* nodes, uint32_t n_nodes, const tt_light_tri* ltris, uint32_t n_ltris,
+                           const tt_light_mesh* lmeshes, uint32_t n_lmeshes, const tt_cuda_triangle* tris,
+                           uint32_t n_tris, const tt_mesh_data* meshdata, uint32_t n_mesh, const tt_trace_params* p,
+                           const tt_ray_data* global_rays, int32_t frames, int32_t max_bounce, uint32_t frame_pixels,
+                           uint32_t terrains, tt_light_sample* samples, tt_shadow_ray* shadow_rays,
+                           uint32_t* n_shadow);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,24 @@ struct SceneDev {
     std::vector<tt_terrain> terrains_host;  // each march launch carries its terrain in the kernel arguments
     DevBuf<uint16_t> hmap;        // binary16 texels
     uint32_t hmap_w = 0, hmap_h = 0;
+    // Lights (tt_scene_upload_lights): LightNodes, LightTriangles, _LightMeshes and their host mirrors (what
+    // tt_scene_update_light_nodes validates against). They index the geometry, so they go when it is replaced.
+    DevBuf<tt_light_node> lnodes;
+    DevBuf<tt_light_tri> ltris;
+    DevBuf<tt_light_mesh> lmeshes;
+    uint32_t n_lnodes = 0;  // 0: no lights
+    std::vector<tt_light_node> lnodes_host;
+    std::vector<tt_light_tri> ltris_host;
+    std::vector<tt_light_mesh> lmeshes_host;
+    void release_lights() {
+        lnodes.release();
+        ltris.release();
+        lmeshes.release();
+        n_lnodes = 0;
+        lnodes_host.clear();
+        ltris_host.clear();
+        lmeshes_host.clear();
+    }
 
     // what tt_scene_upload / tt_scene_assemble_objects replace (the atlases and terrains have calls of their own)
     void release_geometry() {
@@ -134,6 +152,7 @@ struct SceneDev {
         mesh_raw.release();
         mesh.release();
         leaf.release();
+        release_lights();
     }
     // a borrower's view of a lender's scene: everything but the TLAS side
     void borrow_shared(const SceneDev& o) {
@@ -149,6 +168,10 @@ struct SceneDev {
         terrains.borrow(o.terrains);
         hmap.borrow(o.hmap);
         terrains_host = o.terrains_host;
+        lnodes.borrow(o.lnodes);
+        ltris.borrow(o.ltris);
+        lmeshes.borrow(o.lmeshes);
+        n_lnodes = o.n_lnodes;
         hmap_w = o.hmap_w;
         hmap_h = o.hmap_h;
         tex_w = o.tex_w;
@@ -184,6 +207,7 @@ struct tt_ctx {
     uint32_t ring_n = 0, ring_base = 0;
     bool timing = true;  // tt_ctx_set_timing: asynchronous launches record their HIP-event pair
     uint32_t frame_pixels = 0;  // tt_ctx_set_frame_pixels: batched frames' bounce random numbers (0: off)
+    bool group_member = false;  // a tt_group member's context: groups carry no lights (tt_scene_upload_lights refuses)
     bool lib_stream = false;    // stream is one of tt_stream_create's (tt_shutdown / the exit teardown may end it)
     std::string err;
     // scene
@@ -245,6 +269,8 @@ struct tt_ctx {
     DevBuf<uint2> spill;        // deep traversal-stack entries (tt_trace_spill_entries() per thread)
     uint32_t spill_threads = 0; // grid threads the spill area is sized for (max over all grids)
     DevBuf<tt_shadow_ray> st_shadow;
+    DevBuf<tt_light_sample> st_samples;  // tt_emit_nee with host pointers
+    DevBuf<uint32_t> nee_ctl;            // tt_emit_nee: survivor count, tile ticket, one look-back word per tile
     DevBuf<float4> st_vis;
     DevBuf<float4> st_nee;
     DevBuf<tt_cache_data> st_cache;

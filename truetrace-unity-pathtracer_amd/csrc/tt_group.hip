@@ -32,6 +32,9 @@
 
 #include "../../include/truetrace_hip.h"
 
+// tt_lights.hip: a group member's contexts carry no lights (tt_scene_upload_lights / tt_emit_nee refuse on them)
+void tt_ctx_mark_group_member(tt_ctx* c);
+
 hipError_t tt_launch_generate_list(const float* c2w, const float* ip, const uint32_t* pixels, uint32_t n,
                                    uint32_t batch, uint32_t w, uint32_t h, float near_plane, float far_plane,
                                    int32_t jitter, int32_t frames, int32_t max_bounce, tt_ray_data* rays,
@@ -285,6 +288,7 @@ tt_status setup(tt_group* g, const tt_group_config* cfg) {
             c.device = mb.device;
             c.stream = mb.stream[s];
             if (tt_ctx_create(&c, &mb.ctx[s]) != TT_OK) return gfail(g, TT_ERR_HIP, "tt_ctx_create on device %d", mb.device);
+            tt_ctx_mark_group_member(mb.ctx[s]);
             (void)tt_ctx_set_timing(mb.ctx[s], 0);  // no per-launch event pair (a host turns it on per context)
             if (B > 1) (void)tt_ctx_set_frame_pixels(mb.ctx[s], (uint32_t)WH);
             G_HIP(g, hipSetDevice(mb.device));
@@ -518,6 +522,7 @@ tt_status reupload(tt_group* g, Up up) {
             c.device = mb.device;
             c.stream = mb.stream[s];
             if (tt_ctx_create(&c, &mb.ctx[s]) != TT_OK) return gfail(g, TT_ERR_HIP, "tt_ctx_create on device %d", mb.device);
+            tt_ctx_mark_group_member(mb.ctx[s]);
             (void)tt_ctx_set_timing(mb.ctx[s], 0);
             if (g->B > 1) (void)tt_ctx_set_frame_pixels(mb.ctx[s], g->W * g->H);
             G_TT(g, mb.ctx[s], tt_ctx_share_scene(mb.ctx[s], c0));

@@ -9,6 +9,7 @@
 #include "tt_assemble.h"
 #include "tt_build.h"
 #include "tt_ctx.h"
+#include "tt_lights_check_host.h"
 #include "tt_refit_items_host.h"
 #include "tt_tlas_host.h"
 
@@ -1333,6 +1334,23 @@ tt_status tt_scene_update_meshdata(tt_ctx* c, uint32_t first, uint32_t count, co
     if (!added.empty()) {
         h.blas_ok.insert(h.blas_ok.end(), added.begin(), added.end());
         std::sort(h.blas_ok.begin(), h.blas_ok.end());
+    }
+    // the lights index _MeshData (LightNodeOffset, TriOffset): a record that moves either is checked with them
+    if (c->scene.n_lnodes != 0 && !c->ovl) {
+        bool moved = false;
+        for (uint32_t i = 0; i < count && !moved; i++)
+            moved = md[i].LightNodeOffset != h.mesh[first + i].LightNodeOffset || md[i].TriOffset != h.mesh[first + i].TriOffset;
+        if (moved) {
+            std::vector<tt_mesh_data> next = h.mesh;
+            std::memcpy(next.data() + first, md, sizeof(tt_mesh_data) * count);
+            const SceneDev& d = c->scene;
+            std::string why;
+            if (tt_lcheck::validate(tt_lcheck::Lights{d.lnodes_host.data(), (uint32_t)d.lnodes_host.size(), d.ltris_host.data(),
+                                                      (uint32_t)d.ltris_host.size(), d.lmeshes_host.data(),
+                                                      (uint32_t)d.lmeshes_host.size()},
+                                    next.data(), (uint32_t)next.size(), h.n_tris, why) != TT_OK)
+                return fail(c, TT_ERR_INVALID_ARG, "light validation failed after meshdata update: %s", why.c_str());
+        }
     }
     std::memcpy(h.mesh.data() + first, md, sizeof(tt_mesh_data) * count);
     TT_HIP(c, hipSetDevice(c->device));

@@ -122,3 +122,51 @@ def c5_san_miguel_manager(seed: int = C5_SEED, n_tris: int = C5_TRIS):
     am = tthip.AssetManager()
     am.add_parent(tthip.Blas(tthip.Mesh.san_miguel(seed, n_tris)), None, np.zeros(8, tthip.MAT_DTYPE))
     return am, am.build()
+
+
+# ---------------------------------------------------------------- emissive variants (the light BVH, tt_emit_nee)
+def ceiling_panels(bb_max, bb_min, nx: int, nz: int, fill: float = 0.6, drop: float = 0.02):
+    """nx x nz emissive quads under the ceiling of a box: (positions, normals), unshared vertices, facing down.
+    The panels tile the central `fill` of the box's x-z extent with gaps half a panel wide, `drop` of the height
+    below the top."""
+    bb_max, bb_min = np.asarray(bb_max, np.float64), np.asarray(bb_min, np.float64)
+    size = bb_max - bb_min
+    y = bb_max[1] - drop * size[1]
+    x0, z0 = bb_min[0] + 0.5 * (1 - fill) * size[0], bb_min[2] + 0.5 * (1 - fill) * size[2]
+    px, pz = fill * size[0] / (1.5 * nx - 0.5), fill * size[2] / (1.5 * nz - 0.5)
+    v = []
+    for i in range(nx):
+        for j in range(nz):
+            a = np.array([x0 + 1.5 * i * px, y, z0 + 1.5 * j * pz])
+            ex, ez = np.array([px, 0, 0]), np.array([0, 0, pz])
+            v += [a, a + ex, a + ex + ez, a, a + ex + ez, a + ez]  # counter-clockwise seen from below
+    pos = np.asarray(v, np.float32)
+    return pos, np.tile(np.float32([0, -1, 0]), (len(pos), 1))
+
+
+def _with_panels(base_blas, base_materials: int, nx: int, nz: int):
+    """(Scene, Lights): the base mesh as mesh record 0, its ceiling panels as record 1, every panel triangle a light."""
+    am = tthip.AssetManager()
+    am.add_parent(base_blas, None, np.zeros(base_materials, tthip.MAT_DTYPE))
+    box = am.build().meta["mesh_aabbs"][0]
+    pos, nrm = ceiling_panels(box[0:3], box[3:6], nx, nz)
+    panel_mats = np.zeros(1, tthip.MAT_DTYPE)
+    panel_mats["emmissive"] = 1.0
+    panels = tthip.ArrayMesh(pos, np.arange(len(pos), dtype=np.int32), normals=nrm)
+    am.add_parent(tthip.Blas(panels), None, panel_mats)
+    scene = am.build()
+    off = int(scene.meshdata["TriOffset"][1])
+    n = len(pos) // 3
+    parent = tthip.light_tris_from_mesh(scene.tris[off:off + n], np.arange(n, dtype=np.uint32))
+    lights = tthip.lights_assemble([parent], [(0, 1, np.eye(4))], scene.meshdata)
+    return scene, lights
+
+
+def c1_cornell_lights(nx: int = 1, nz: int = 1):
+    """C1 with one emissive ceiling panel (2 light triangles): (Scene, Lights)."""
+    return _with_panels(tthip.Blas(tthip.Mesh.cornell()), 4, nx, nz)
+
+
+def c2_sponza_lights(seed: int = C2_SEED, n_tris: int = C2_TRIS, nx: int = 8, nz: int = 4):
+    """C2 with an 8 x 4 grid of emissive ceiling panels (64 light triangles): (Scene, Lights)."""
+    return _with_panels(tthip.Blas(tthip.Mesh.sponza(seed, n_tris)), 7, nx, nz)

@@ -48,6 +48,8 @@ TT_ENQUEUE_TERRAIN_BOUNCE = 1 << 8  # tt_enqueue_diffuse_bounce(_indirect): terr
 TT_TRACE_FORM_NONE, TT_TRACE_FORM_GENERIC, TT_TRACE_FORM_LEAF = 0, 1, 2
 # tt_tlas_root_form: what a TLAS's node 0 is (2: one leaf of one instance, the leaf-TLAS kernels' condition)
 TT_ROOT_GENERIC, TT_ROOT_ONE_LEAF, TT_ROOT_ONE_INSTANCE = 0, 1, 2
+TT_NEE_NEGATIVE_T = 1 << 9  # tt_emit_nee(_indirect): every written t negated (the PrimaryNEERay / Indirect form)
+TT_LIGHT_MAX_REPS = 322     # SampleLightBVH's loop bound (CommonData.cginc:1132)
 TT_SHADOW_RADIANCE_CACHE = 1 << 7    # RadianceCache define (GlobalDefines.cginc:15) for tt_trace_shadow_ex
 TT_SHADOW_VISIBILITY_CHECK = 1 << 8  # VisabilityCheckCompute semantics (CommonData.cginc:710-819)
 TT_TERRAIN_MESH_ID = 9999999   # mesh_id of a terrain hit record (IntersectionKernels.compute:686)
@@ -104,6 +106,27 @@ CACHE_DTYPE = np.dtype([("samples", "<u4", (4, 2)), ("throughput", "<u4"), ("pat
                         ("CurrentIlluminance", "<u4"), ("Norm", "<u4")])
 assert CACHE_DTYPE.itemsize == 48 and CACHE_DTYPE.fields["CurrentIlluminance"][1] == 40
 TT_FLAG_IS_BACKGROUND, TT_FLAG_SHADOW_CASTER = 5, 6
+
+
+# LightBVHData / LightTriData / LightMeshData (CommonData.cginc:987-994, :297-314), tt_light_sample, tt_light_bounds
+LIGHT_NODE_DTYPE = np.dtype([("BBMax", "<f4", 3), ("BBMin", "<f4", 3), ("w", "<u4"), ("phi", "<f4"),
+                             ("cosTheta_oe", "<u4"), ("left", "<i4")])
+LIGHT_TRI_DTYPE = np.dtype([("pos0", "<f4", 3), ("posedge1", "<f4", 3), ("posedge2", "<f4", 3), ("TriTarget", "<u4")])
+LIGHT_MESH_DTYPE = np.dtype([("Center", "<f4", 3), ("StartIndex", "<i4"), ("IndexEnd", "<i4"), ("MatOffset", "<i4"),
+                             ("LockedMeshIndex", "<i4")])
+LIGHT_SAMPLE_DTYPE = np.dtype([("light_tri", "<i4"), ("mesh_index", "<i4"), ("agg_tri", "<i4"), ("steps", "<i4"),
+                               ("weight", "<f4"), ("area", "<f4"), ("position", "<f4", 3), ("normal", "<f4", 3)])
+LIGHT_BOUNDS_DTYPE = np.dtype([("BBMax", "<f4", 3), ("BBMin", "<f4", 3), ("w", "<f4", 3), ("phi", "<f4"),
+                               ("cosTheta_o", "<f4"), ("cosTheta_e", "<f4"), ("LightCount", "<i4"), ("Pad1", "<f4")])
+assert (LIGHT_NODE_DTYPE.itemsize, LIGHT_TRI_DTYPE.itemsize, LIGHT_MESH_DTYPE.itemsize, LIGHT_SAMPLE_DTYPE.itemsize) == (40, 40, 28, 48)
+
+
+class LightParent(C.Structure):
+    _fields_ = [("tris", C.c_void_p), ("normals", C.c_void_p), ("n_tris", C.c_uint32)]
+
+
+class LightInstance(C.Structure):
+    _fields_ = [("parent", C.c_uint32), ("mesh_index", C.c_int32), ("local_to_world", C.c_float * 16)]
 
 
 class ShadowParams(C.Structure):
@@ -231,7 +254,8 @@ HIP_SYMBOLS = ["tt_abi_version", "tt_device_count", "tt_ctx_create", "tt_ctx_des
                "tt_object_destroy", "tt_scene_layout_objects", "tt_scene_layout_counts", "tt_scene_assemble_objects",
                "tt_object_build_device", "tt_object_read", "tt_object_leaf_order_device", "tt_objects_build_device",
                "tt_scene_update_tlas", "tt_tlas_rebuild", "tt_scene_read_tlas_indices", "tt_group_tlas_rebuild",
-               "tt_group_scene_update_tlas", "tt_blas_refit_many", "tt_blas_refit_items_validate"]
+               "tt_group_scene_update_tlas", "tt_blas_refit_many", "tt_blas_refit_items_validate", "tt_lights_validate",
+               "tt_scene_upload_lights", "tt_scene_update_light_nodes", "tt_emit_nee", "tt_emit_nee_indirect"]
 SCENE_SYMBOLS = ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_blas_free", "tt_scene_assemble",
                  "tt_scene_build_get_info", "tt_scene_build_copy", "tt_scene_build_free", "tt_pack_octahedral",
                  "tt_bvh2_build", "tt_dotnet_sort_by_key", "tt_synth_cornell", "tt_synth_soup", "tt_synth_sponza",
@@ -240,7 +264,9 @@ SCENE_SYMBOLS = ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_blas_f
                  "tt_blas_build_from_bvh2", "tt_blas_build_from_cwbvh", "tt_blas_prepare",
                  "tt_blas_build_from_cwbvh_prepared", "tt_blas_prep_free", "tt_terrain_trace_host",
                  "tt_terrain_trace_detail_host", "tt_terrain_occluded_host", "tt_terrain_normal_host",
-                 "tt_scene_assemble_tlas", "tt_scene_build_get_totals", "tt_tlas_build"]
+                 "tt_scene_assemble_tlas", "tt_scene_build_get_totals", "tt_tlas_build", "tt_light_tris_from_mesh",
+                 "tt_light_bvh_build_mesh", "tt_light_bvh_build_tlas", "tt_light_bounds_transform", "tt_lights_assemble",
+                 "tt_emit_nee_host"]
 
 
 def scene_lib():
@@ -302,6 +328,17 @@ def scene_lib():
         L.tt_terrain_bounce_host.argtypes = [vp, u32, vp, u32, u32, C.POINTER(TraceParams), vp, i32, i32, u32, vp, vp]
         for s in ["tt_terrain_trace_host", "tt_terrain_trace_detail_host", "tt_terrain_occluded_host",
                   "tt_terrain_normal_host", "tt_terrain_bounce_host"]:
+            getattr(L, s).restype = i32
+        L.tt_light_tris_from_mesh.argtypes = [vp, u32, vp, u32, vp, vp, vp]
+        L.tt_light_bvh_build_mesh.argtypes = [vp, vp, u32, vp, vp]
+        L.tt_light_bvh_build_tlas.argtypes = [vp, u32, vp]
+        L.tt_light_bounds_transform.argtypes = [vp, vp, vp]
+        L.tt_lights_assemble.argtypes = [C.POINTER(LightParent), u32, C.POINTER(LightInstance), u32, vp, u32, vp,
+                                         C.POINTER(u32), vp, C.POINTER(u32), vp]
+        L.tt_emit_nee_host.argtypes = [vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, C.POINTER(TraceParams), vp, i32, i32,
+                                       u32, u32, vp, vp, C.POINTER(u32)]
+        for s in ["tt_light_tris_from_mesh", "tt_light_bvh_build_mesh", "tt_light_bvh_build_tlas",
+                  "tt_light_bounds_transform", "tt_lights_assemble", "tt_emit_nee_host"]:
             getattr(L, s).restype = i32
         for s in ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_scene_assemble", "tt_scene_build_get_info",
                   "tt_scene_build_copy", "tt_bvh2_build", "tt_synth_cornell", "tt_synth_soup", "tt_synth_sponza",
@@ -404,6 +441,15 @@ def hip_lib():
             L.tt_blas_refit_many.argtypes = [vp, C.POINTER(BlasRefitItem), u32, u32, vp, vp]
             L.tt_blas_refit_items_validate.argtypes = [C.POINTER(BlasRefitItem), u32, vp, u32, u32, u32, C.c_char_p, u32]
             for s in ["tt_blas_refit_many", "tt_blas_refit_items_validate"]:
+                getattr(L, s).restype = i32
+        if hasattr(L, "tt_emit_nee"):  # (absent from older libraries)
+            L.tt_lights_validate.argtypes = [vp, u32, vp, u32, vp, u32, vp, u32, u32, C.c_char_p, u32]
+            L.tt_scene_upload_lights.argtypes = [vp, vp, u32, vp, u32, vp, u32]
+            L.tt_scene_update_light_nodes.argtypes = [vp, u32, u32, vp]
+            L.tt_emit_nee.argtypes = [vp, C.POINTER(TraceParams), vp, i32, i32, vp, vp, C.POINTER(u32)]
+            L.tt_emit_nee_indirect.argtypes = [vp, C.POINTER(TraceParams), vp, vp, i32, i32, vp, vp, vp]
+            for s in ["tt_lights_validate", "tt_scene_upload_lights", "tt_scene_update_light_nodes", "tt_emit_nee",
+                      "tt_emit_nee_indirect"]:
                 getattr(L, s).restype = i32
         L.tt_bvh2_build_device.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(u32)]
         L.tt_blas_build_device.argtypes = [vp, vp, u32, vp, vp, u32, C.POINTER(u32), vp, C.POINTER(u32)]
@@ -530,6 +576,100 @@ def terrain_bounce_host(terrains, heightmap, rays, n_rays, bounce, far_plane, wi
                                               C.byref(p), _ptr(rays), frames, max_bounce, frame_pixels, _ptr(out),
                                               _ptr(sv)), "tt_terrain_bounce_host")
     return out[:n_rays], sv[:n_rays]
+
+
+# ---------------------------------------------------------------- lights
+@dataclass
+class Lights:
+    """LightNodes / LightTriangles / _LightMeshes as tt_scene_upload_lights takes them."""
+    nodes: np.ndarray
+    tris: np.ndarray
+    meshes: np.ndarray
+
+
+def lights_validate(lights: "Lights", meshdata, n_scene_tris: int):
+    """tt_lights_validate (host only): (status, reason) of what tt_scene_upload_lights would answer."""
+    md = np.ascontiguousarray(meshdata, MESH_DTYPE)
+    why = C.create_string_buffer(512)
+    st = hip_lib().tt_lights_validate(_ptr(lights.nodes), len(lights.nodes), _ptr(lights.tris), len(lights.tris),
+                                      _ptr(lights.meshes), len(lights.meshes), _ptr(md), len(md), int(n_scene_tris), why, 512)
+    return st, why.value.decode()
+
+
+def light_tris_from_mesh(tris, targets, normals=None):
+    """tt_light_tris_from_mesh: (LightTriData, normals [n, 3]) of the triangles `targets` of a mesh's records."""
+    t = np.ascontiguousarray(tris, TRI_DTYPE)
+    tg = np.ascontiguousarray(targets, np.uint32)
+    nr = None if normals is None else np.ascontiguousarray(normals, np.float32)
+    out = np.zeros(len(tg), LIGHT_TRI_DTYPE)
+    on = np.zeros((len(tg), 3), np.float32)
+    _check(scene_lib().tt_light_tris_from_mesh(_ptr(t), len(t), _ptr(tg), len(tg), _ptr(nr), _ptr(out), _ptr(on)),
+           "tt_light_tris_from_mesh")
+    return out, on
+
+
+def light_bvh_build_mesh(ltris, normals):
+    """tt_light_bvh_build_mesh: (2 n nodes, the root's LightBounds)."""
+    lt = np.ascontiguousarray(ltris, LIGHT_TRI_DTYPE)
+    nr = np.ascontiguousarray(normals, np.float32)
+    nodes = np.zeros(2 * len(lt), LIGHT_NODE_DTYPE)
+    root = np.zeros(1, LIGHT_BOUNDS_DTYPE)
+    _check(scene_lib().tt_light_bvh_build_mesh(_ptr(lt), _ptr(nr), len(lt), _ptr(nodes), _ptr(root)), "tt_light_bvh_build_mesh")
+    return nodes, root
+
+
+def light_bvh_build_tlas(bounds):
+    b = np.ascontiguousarray(bounds, LIGHT_BOUNDS_DTYPE)
+    nodes = np.zeros(2 * len(b), LIGHT_NODE_DTYPE)
+    _check(scene_lib().tt_light_bvh_build_tlas(_ptr(b), len(b), _ptr(nodes)), "tt_light_bvh_build_tlas")
+    return nodes
+
+
+def light_bounds_transform(root, local_to_world):
+    """tt_light_bounds_transform: local_to_world is a row-major (math convention) 4x4, as trs_matrix returns."""
+    r = np.ascontiguousarray(root, LIGHT_BOUNDS_DTYPE)
+    m = unity_colmajor(np.asarray(local_to_world))
+    out = np.zeros(1, LIGHT_BOUNDS_DTYPE)
+    _check(scene_lib().tt_light_bounds_transform(_ptr(r), _ptr(m), _ptr(out)), "tt_light_bounds_transform")
+    return out
+
+
+def lights_assemble(parents, instances, meshdata) -> "Lights":
+    """tt_lights_assemble. parents: [(LightTriData, normals)], instances: [(parent, mesh_index, local_to_world
+    row-major 4x4)]; meshdata (MESH_DTYPE) gets LightNodeOffset / LightTriCount in place."""
+    assert meshdata.dtype == MESH_DTYPE and meshdata.flags["C_CONTIGUOUS"]
+    keep = [(np.ascontiguousarray(t, LIGHT_TRI_DTYPE), np.ascontiguousarray(n, np.float32)) for t, n in parents]
+    P = (LightParent * len(keep))()
+    for k, (t, n) in enumerate(keep):
+        P[k].tris, P[k].normals, P[k].n_tris = _ptr(t), _ptr(n), len(t)
+    I = (LightInstance * len(instances))()
+    for k, (par, mesh_index, l2w) in enumerate(instances):
+        I[k].parent, I[k].mesh_index = par, mesh_index
+        I[k].local_to_world[:] = unity_colmajor(np.asarray(l2w))
+    total = sum(len(t) for t, _ in keep)
+    nodes = np.zeros(2 * len(instances) + 2 * total, LIGHT_NODE_DTYPE)
+    tris = np.zeros(total, LIGHT_TRI_DTYPE)
+    meshes = np.zeros(len(instances), LIGHT_MESH_DTYPE)
+    nn, nt = C.c_uint32(), C.c_uint32()
+    _check(scene_lib().tt_lights_assemble(P, len(keep), I, len(instances), _ptr(meshdata), len(meshdata), _ptr(nodes),
+                                          C.byref(nn), _ptr(tris), C.byref(nt), _ptr(meshes)), "tt_lights_assemble")
+    return Lights(nodes[:nn.value].copy(), tris[:nt.value].copy(), meshes)
+
+
+def emit_nee_host(lights: "Lights", scene, rays, n_rays, bounce, far_plane, width, height, frames=0, max_bounce=3,
+                  frame_pixels=0, terrains=False, flags=0, check: bool = True):
+    """tt_emit_nee_host: (samples [n_rays], shadow rays [n_shadow]) of the scalar reference of tt_emit_nee."""
+    p = TraceParams(n_rays=n_rays, bounce=bounce, far_plane=far_plane, screen_width=width, screen_height=height, flags=flags)
+    smp = np.zeros(max(1, n_rays), LIGHT_SAMPLE_DTYPE)
+    out = np.zeros(max(1, n_rays), SHADOW_DTYPE)
+    n = C.c_uint32()
+    st = scene_lib().tt_emit_nee_host(_ptr(lights.nodes), len(lights.nodes), _ptr(lights.tris), len(lights.tris),
+                                      _ptr(lights.meshes), len(lights.meshes), _ptr(scene.tris), len(scene.tris),
+                                      _ptr(scene.meshdata), len(scene.meshdata), C.byref(p), _ptr(rays), frames,
+                                      max_bounce, frame_pixels, 1 if terrains else 0, _ptr(smp), _ptr(out), C.byref(n))
+    if check:
+        _check(st, "tt_emit_nee_host")
+    return smp[:n_rays], out[:n.value].copy()
 
 
 # ---------------------------------------------------------------- matrices
@@ -1663,6 +1803,47 @@ class Engine:
                                                        max_bounce, _ptr(n_next_dev))
         if check:
             self._check(st, "tt_enqueue_diffuse_bounce_indirect")
+        return st
+
+
+    def upload_lights(self, lights: "Lights", check: bool = True):
+        """tt_scene_upload_lights: the scene's LightNodes / LightTriangles / _LightMeshes."""
+        st = self.L.tt_scene_upload_lights(self.h, _ptr(lights.nodes), len(lights.nodes), _ptr(lights.tris),
+                                           len(lights.tris), _ptr(lights.meshes), len(lights.meshes))
+        if check:
+            self._check(st, "tt_scene_upload_lights")
+        return st
+
+    def update_light_nodes(self, first: int, nodes: np.ndarray, check: bool = True):
+        st = self.L.tt_scene_update_light_nodes(self.h, first, len(nodes), _ptr(nodes))
+        if check:
+            self._check(st, "tt_scene_update_light_nodes")
+        return st
+
+    def emit_nee(self, rays, n_rays, bounce, far_plane, width, height, frames=0, max_bounce=3, samples=None,
+                 shadow_rays=None, device=False, asynchronous=False, flags=0, check: bool = True):
+        """tt_emit_nee: the survivor count (None when asynchronous); samples / shadow_rays are filled in place.
+        check=False returns (status, count)."""
+        p = TraceParams(n_rays=n_rays, bounce=bounce, far_plane=far_plane, screen_width=width, screen_height=height,
+                        flags=flags | (TT_TRACE_DEVICE_PTRS if device else 0) | (TT_TRACE_ASYNC if asynchronous else 0))
+        n = C.c_uint32()
+        st = self.L.tt_emit_nee(self.h, C.byref(p), _ptr(rays), frames, max_bounce, _ptr(samples), _ptr(shadow_rays),
+                                None if asynchronous else C.byref(n))
+        if not check:
+            return st, n.value
+        self._check(st, "tt_emit_nee")
+        return None if asynchronous else n.value
+
+    def emit_nee_indirect(self, rays, n_rays_dev, capacity, n_shadow_dev, bounce, far_plane, width, height, frames=0,
+                          max_bounce=3, samples=None, shadow_rays=None, flags=0, check: bool = True):
+        """tt_emit_nee_indirect: the traced count from n_rays_dev (None: capacity), the survivor count written to the
+        device uint32 n_shadow_dev; no synchronization."""
+        p = TraceParams(n_rays=capacity, bounce=bounce, far_plane=far_plane, screen_width=width, screen_height=height,
+                        flags=flags | TT_TRACE_DEVICE_PTRS)
+        st = self.L.tt_emit_nee_indirect(self.h, C.byref(p), _ptr(n_rays_dev), _ptr(rays), frames, max_bounce,
+                                         _ptr(samples), _ptr(shadow_rays), _ptr(n_shadow_dev))
+        if check:
+            self._check(st, "tt_emit_nee_indirect")
         return st
 
 
