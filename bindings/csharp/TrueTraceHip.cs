@@ -25,6 +25,7 @@ namespace TrueTrace.Hip
         AdaptiveOrder = 1u << 7,     // dequeue the previous launch's costliest 8x8 tiles first (same results)
         TerrainBounce = 1u << 8,     // tt_enqueue_diffuse_bounce(_indirect): terrain hits bounce off the terrain
         NeeNegativeT = 1u << 9,      // tt_emit_nee(_indirect): every written t negated (PrimaryNEERay / Indirect form)
+        LightRefitConservative = 1u << 10,  // tt_lights_refit: every cone contains the cones below it
         RadianceCache = 1u << 7,     // tt_trace_shadow_ex: the RadianceCache define (GlobalDefines.cginc:15)
         VisibilityCheck = 1u << 8    // tt_trace_shadow_ex: VisabilityCheckCompute (CommonData.cginc:710-819)
     }
@@ -101,6 +102,15 @@ namespace TrueTrace.Hip
         public TTBlasRefitPart* parts;
         public uint nParts;
         public float* localToWorld;  // null, or 16 floats column-major (host memory)
+    }
+
+    /// LightBVHTransform (AssetManager.cs:1311-1314), 68 bytes, blittable: a light mesh's localToWorldMatrix
+    /// (column-major, as UnityEngine.Matrix4x4 lies in memory) and the root of its mesh tree (LightNodeOffset).
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct TTLightTransform
+    {
+        public fixed float transform[16];
+        public int solidOffset;
     }
 
     /// Generate's camera (RayGenKernels.compute:40-57): Unity's cameraToWorldMatrix and projectionMatrix.inverse,
@@ -293,6 +303,12 @@ namespace TrueTrace.Hip
             IntPtr tris, uint nTris, IntPtr meshes, uint nMeshes);
         [DllImport(Lib)] public static extern TTStatus tt_scene_update_light_nodes(IntPtr ctx, uint first, uint count,
             IntPtr nodes);
+        // LightBVHRefitter.compute per frame: the light trees of the listed meshes (after tt_blas_refit(_many)), then
+        // the light TLAS under this frame's transforms (null: no TLAS pass); the read-backs of what it wrote
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_lights_refit(IntPtr ctx, uint* meshIndices, uint nMeshIndices,
+            TTLightTransform* transforms, uint nTransforms, uint flags);
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_scene_read_light_nodes(IntPtr ctx, uint first, uint count, void* nodes);
+        [DllImport(Lib)] public static extern unsafe TTStatus tt_scene_read_light_tris(IntPtr ctx, uint first, uint count, void* tris);
         [DllImport(Lib)] public static extern TTStatus tt_emit_nee(IntPtr ctx, ref TTTraceParams p, IntPtr globalRays,
             int framesAccumulated, int maxBounce, IntPtr samples, IntPtr shadowRays, out uint nShadow);
         [DllImport(Lib)] public static extern TTStatus tt_emit_nee_indirect(IntPtr ctx, ref TTTraceParams p, IntPtr nRaysDev,
@@ -744,6 +760,33 @@ namespace TrueTrace.Hip
         {
             fixed (float* b = meshAabbs)
                 Check(Native.tt_tlas_refit(m_ctx, (uint)nTlasNodes, b, (uint)(meshAabbs.Length / 6), 0));
+        }
+
+        /// LightBVHRefitter.compute (ParentObject.RefitMesh, AssetManager.RefitTLAS): refits the light trees of
+        /// the listed _MeshData records from their refit triangles, then the light TLAS under `transforms` (one per
+        /// light mesh; null: no TLAS pass). Call after RefitMeshes and before RefitTLAS and the frame's traces.
+        public unsafe void RefitLights(uint[] meshIndices, TTLightTransform[] transforms, TTTraceFlags flags = TTTraceFlags.None)
+        {
+            fixed (uint* mi = meshIndices)
+            fixed (TTLightTransform* x = transforms)
+                Check(Native.tt_lights_refit(m_ctx, mi, (uint)(meshIndices?.Length ?? 0), x, (uint)(transforms?.Length ?? 0),
+                                             (uint)flags));
+        }
+
+        /// LightNodes[first, first + count) as the device holds them (40 bytes each) into `nodes`.
+        public unsafe void ReadLightNodes(uint first, uint count, byte[] nodes)
+        {
+            if (nodes.Length < 40 * (long)count) throw new ArgumentException("nodes is too small");
+            fixed (byte* p = nodes)
+                Check(Native.tt_scene_read_light_nodes(m_ctx, first, count, p));
+        }
+
+        /// LightTriangles[first, first + count) as the device holds them (40 bytes each) into `tris`.
+        public unsafe void ReadLightTris(uint first, uint count, byte[] tris)
+        {
+            if (tris.Length < 40 * (long)count) throw new ArgumentException("tris is too small");
+            fixed (byte* p = tris)
+                Check(Native.tt_scene_read_light_tris(m_ctx, first, count, p));
         }
 
         /// CorrectRefit + the swap in RefitTLAS (AssetManager.cs:1423-1529) on the device: a new TLAS over this

@@ -1133,6 +1133,65 @@ tt_status tt_scene_upload_lights(tt_ctx* ctx, const tt_light_node* nodes, uint32
  * borrowers' launches like tt_scene_update_nodes. */
 tt_status tt_scene_update_light_nodes(tt_ctx* ctx, uint32_t first, uint32_t count, const tt_light_node* nodes);
 
+/* LightBVHTransform, 68 B (AssetManager.cs:1311-1314): a light mesh's current localToWorldMatrix and the root of
+ * its mesh tree (its _MeshData record's LightNodeOffset). Transform is column-major like every other matrix
+ * here: HLSL mat[r][c] is element (r, c) = Transform[c * 4 + r]. */
+typedef struct tt_light_transform {
+    float Transform[16];
+    int32_t SolidOffset;
+} tt_light_transform;
+TT_STATIC_ASSERT(sizeof(tt_light_transform) == 68, "LightBVHTransform is 68 bytes");
+
+/* tt_lights_refit flag, beyond TT_TRACE_DEVICE_PTRS / TT_TRACE_ASYNC: every cone contains the cones below it.
+ * The default is the reference's drop-in arithmetic with its two kept exceptions: Rotate
+ * returns m * transpose(m), so a union cone keeps its first child's axis and need not contain the second; a
+ * TLAS leaf's axis goes through the matrix of absolute values. With the flag Rotate applies m itself and the
+ * leaf axis is the matrix times the root's axis, normalized. */
+enum { TT_LIGHT_REFIT_CONSERVATIVE = 1u << 10 };
+/* The most light nodes tt_lights_refit addresses (40-byte nodes behind 32-bit byte offsets of a 2 GiB buffer
+ * resource); tt_scene_upload_lights takes more, a refit of them is TT_ERR_UNSUPPORTED. */
+#define TT_LIGHT_REFIT_MAX_NODES 53687091u
+
+/* The per-frame refit of the light BVH on the device: LightBVHRefitter.compute's LightRefitKernel (:183-209, with
+ * BVHRefitter.compute's TransferKernel :135-147 in front of it) for every listed mesh, then RefitKernel (:136-157)
+ * over the light TLAS -- what the reference runs every frame from ParentObject.RefitMesh and
+ * AssetManager.RefitTLAS. Two launches on the context stream, each a thread per leaf that climbs (no dispatch
+ * per depth level), under one tt_timing_read entry.
+ *   mesh_indices  host memory, may be empty: the _MeshData records whose light trees follow their triangles.
+ *                 Call after tt_blas_refit(_many) of those meshes. Per light-triangle leaf: pos0 / posedge1 /
+ *                 posedge2 of its LightTriangles row are copied from the 88-byte triangle at TriTarget +
+ *                 TriOffset (TriTarget stays); the leaf's BBMax, BBMin, w and phi (the triangle's area) are
+ *                 rewritten (cosTheta_oe and left stay); every interior node above is the Union of its children.
+ *   transforms    nullable: NULL means no TLAS pass. Otherwise n_transforms must equal the light-mesh count;
+ *                 TLAS leaf -(left + 1) = i takes transforms[i] and the node at its SolidOffset (after the mesh
+ *                 pass, so it sees a refit root; instances that share a tree read the same root). With
+ *                 TT_TRACE_DEVICE_PTRS the array is in HBM and an out-of-range SolidOffset reads zeros (D3D); a
+ *                 SolidOffset there that names a TLAS node reads a node the same launch rewrites (order-dependent
+ *                 bytes: the caller's error). A host array is checked instead: every SolidOffset must be the root
+ *                 of a mesh tree, that is the LightNodeOffset of some light mesh's record.
+ *   flags         TT_TRACE_DEVICE_PTRS, TT_TRACE_ASYNC (return without waiting; host arrays are copied to pinned
+ *                 staging before the call returns, so either form may be asynchronous),
+ *                 TT_LIGHT_REFIT_CONSERVATIVE.
+ * Nodes no descent reaches (slot 1 of every tree, unused tail slots) keep their bytes. A moved light instance
+ * also needs its _MeshData record rewritten (tt_scene_update_meshdata): the emit reads its W2L.
+ * The host mirrors keep structure only after a refit: tt_scene_update_light_nodes still validates against them
+ * (a refit never changes a `left`), but boxes, cones and powers are read back with tt_scene_read_light_nodes.
+ * Results are bit-identical to tt_lights_refit_host (truetrace_scene.h) whatever the arrival order.
+ * TT_ERR_INVALID_ARG, with the offending index in tt_last_error: a listed record with LightTriCount == 0 or
+ * without a light tree, two listed records with one LightNodeOffset, n_transforms != the light-mesh count, a
+ * host-side SolidOffset that is not a mesh tree's root; lights that tt_lights_validate accepts but no refit can
+ * climb -- a node reached from two trees with distinct LightNodeOffset, or two light meshes naming one tree with
+ * different StartIndex (the validator looks at each light mesh alone); a tt_ctx_share_scene borrower is refused (refit the lender: its
+ * borrowers see it, ordered like tt_scene_update_light_nodes). TT_ERR_NO_SCENE without lights.
+ * TT_ERR_UNSUPPORTED on a frame slot (tt_ctx_share_blas) or a group member, and
+ * with more than TT_LIGHT_REFIT_MAX_NODES light nodes. */
+tt_status tt_lights_refit(tt_ctx* ctx, const uint32_t* mesh_indices, uint32_t n_mesh_indices,
+                          const tt_light_transform* transforms, uint32_t n_transforms, uint32_t flags);
+/* LightNodes[first, first + count) / LightTriangles[first, first + count) as the device holds them, after
+ * everything enqueued on the context stream (synchronizes). A borrower reads its lender's. */
+tt_status tt_scene_read_light_nodes(tt_ctx* ctx, uint32_t first, uint32_t count, tt_light_node* out);
+tt_status tt_scene_read_light_tris(tt_ctx* ctx, uint32_t first, uint32_t count, tt_light_tri* out);
+
 /* Next event estimation toward the scene's emissive triangles for the rays traced at p->bounce: the geometric
  * subset of kernel_shade's NEE block (RayTracingShader.compute:328-344, :391-409, :418-479) for triangle
  * lights, as the enqueue is the subset that produces the next ray. Per hit (t < far_plane, a triangle record):

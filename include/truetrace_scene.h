@@ -257,6 +257,20 @@ tt_status tt_emit_nee_host(const tt_light_node* nodes, uint32_t n_nodes, const t
                            const tt_ray_data* global_rays, int32_t frames, int32_t max_bounce, uint32_t frame_pixels,
                            uint32_t terrains, tt_light_sample* samples, tt_shadow_ray* shadow_rays,
                            uint32_t* n_shadow);
+/* The scalar host reference of tt_lights_refit (truetrace_hip.h): the same arguments over host arrays -- nodes and
+ * ltris are rewritten in place, bit for bit what the device leaves. It evaluates the reference's dispatches in the
+ * reference's order: per listed mesh the transfer, then its tree one depth level after another from the deepest
+ * up; then, with transforms, the TLAS the same way. flags: TT_LIGHT_REFIT_CONSERVATIVE. The lights are checked
+ * with the rules of tt_lights_validate first, the call with tt_lights_refit's; why (nullable) names the index. */
+tt_status tt_lights_refit_host(tt_light_node* nodes, uint32_t n_nodes, tt_light_tri* ltris, uint32_t n_ltris,
+                               const tt_light_mesh* lmeshes, uint32_t n_lmeshes, const tt_cuda_triangle* tris,
+                               uint32_t n_tris, const tt_mesh_data* meshdata, uint32_t n_mesh,
+                               const uint32_t* mesh_indices, uint32_t n_mesh_indices,
+                               const tt_light_transform* transforms, uint32_t n_transforms, uint32_t flags, char* why,
+                               uint32_t why_len);
+/* The pinned asin / acos / sin / cos of the light refit (csrc/tt_light_refit_core.h) over an array, for tests:
+ * fn 0 asin, 1 acos, 2 sin, 3 cos. */
+tt_status tt_light_refit_math(uint32_t fn, const float* in, uint32_t n, float* out);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,8 @@
 
 #include "tt_assemble_host.h"
 #include "tt_device.h"
+#include "tt_light_refit.h"
+#include "tt_light_refit_plan_host.h"
 #include "tt_refit.h"
 
 #define TT_RING 256u
@@ -129,7 +131,31 @@ struct SceneDev {
     std::vector<tt_light_node> lnodes_host;
     std::vector<tt_light_tri> ltris_host;
     std::vector<tt_light_mesh> lmeshes_host;
+    // tt_lights_refit: the plan of what it climbs (built from the mirrors at tt_scene_upload_lights, again after a
+    // tt_scene_update_light_nodes that changed a `left` or a _MeshData update that moved a tree), its device
+    // arrays (made by the first refit after either) and the staging of a call's block table and host transforms
+    struct LightRefit {
+        tt_lplan::Plan plan;
+        bool plan_valid = false, dev_valid = false;
+        DevBuf<int2> up;
+        DevBuf<uint32_t> arrive;
+        DevBuf<int32_t> leaf_node, leaf_row;
+        DevBuf<LightRefitBlock> blocks;
+        DevBuf<tt_light_transform> transforms;
+        void release() {
+            plan = tt_lplan::Plan();
+            plan_valid = dev_valid = false;
+            up.release();
+            arrive.release();
+            leaf_node.release();
+            leaf_row.release();
+            blocks.release();
+            transforms.release();
+        }
+    };
+    LightRefit lrefit;
     void release_lights() {
+        lrefit.release();
         lnodes.release();
         ltris.release();
         lmeshes.release();

@@ -2,6 +2,8 @@
 //  * tt_lights_validate / tt_scene_upload_lights / tt_scene_update_light_nodes: LightNodes, LightTriangles and
 //    _LightMeshes live with the scene's device buffers (SceneDev), checked on the host first
 //    (tt_lights_check_host.h): the kernel below indexes them without bounds checks;
+//  * tt_lights_refit: the host side of the per-frame refit (the plan of tt_light_refit_plan_host.h, the call's
+//    checks and block table); its two launches are tt_light_refit.hip. tt_scene_read_light_nodes / _tris;
 //  * tt_nee_kernel: one lane per traced ray. The hit's frame is the enqueue's own device code (tt_producer.h);
 //    SampleLightBVH, Importance and the emitted record are tt_lights_core.h, the text the host reference builds
 //    too. Per descent step a lane fetches its two children as one 80-byte block (five 128-bit loads) and carries
@@ -13,6 +15,8 @@
 //    ballot / LDS prefix inside the tile, the decoupled look-back over the preceding tiles. LDS holds only that.
 #include "tt_call_host.h"
 #include "tt_ctx.h"
+#include "tt_light_refit.h"
+#include "tt_light_refit_plan_host.h"
 #include "tt_lights_check_host.h"
 #include "tt_lights_core.h"
 #include "tt_producer.h"
@@ -259,6 +263,8 @@ tt_status tt_scene_upload_lights(tt_ctx* c, const tt_light_node* nodes, uint32_t
     d.ltris_host.assign(tris, tris + n_tris);
     d.lmeshes_host.assign(meshes, meshes + n_meshes);
     d.n_lnodes = n_nodes;
+    tt_lplan::build(host_lights(d), c->host.mesh.data(), d.lrefit.plan);  // (its device arrays: the first refit's)
+    d.lrefit.plan_valid = true;
     return TT_OK;
 }
 
@@ -287,7 +293,128 @@ tt_status tt_scene_update_light_nodes(tt_ctx* c, uint32_t first, uint32_t count,
     TT_HIP(c, hipMemcpyAsync(d.lnodes.p + first, pin, sizeof(tt_light_node) * count, hipMemcpyHostToDevice, c->stream));
     TT_HIP(c, stage_end(c));
     TT_HIP(c, w.end());
+    // a changed `left` changes what the refit climbs: its plan is rebuilt by the next tt_lights_refit
+    if (!tt_lplan::same_structure(next.data() + first, d.lnodes_host.data() + first, count)) d.lrefit.plan_valid = false;
     d.lnodes_host.swap(next);
+    return TT_OK;
+}
+
+tt_status tt_lights_refit(tt_ctx* c, const uint32_t* mesh_indices, uint32_t n_mesh_indices, const tt_light_transform* transforms,
+                          uint32_t n_transforms, uint32_t flags) {
+    if (!c) return TT_ERR_INVALID_ARG;
+    TT_REFUSE_DEAD_STREAM(c);
+    if (c->ovl || c->group_member)
+        return fail(c, TT_ERR_UNSUPPORTED, "tt_lights_refit: frame slots (tt_ctx_share_blas) and group members carry no lights");
+    TT_REFUSE_BORROWER(c);
+    if (!c->has_scene || c->scene.n_lnodes == 0) return fail(c, TT_ERR_NO_SCENE, "tt_lights_refit: no lights uploaded");
+    if (flags & ~(uint32_t)(TT_TRACE_DEVICE_PTRS | TT_TRACE_ASYNC | TT_LIGHT_REFIT_CONSERVATIVE))
+        return fail(c, TT_ERR_INVALID_ARG, "tt_lights_refit: unknown flag bits 0x%x", flags);
+    SceneDev& d = c->scene;
+    // the kernels address the nodes through a buffer resource of n * 40 bytes and 32-bit byte offsets
+    if (d.n_lnodes > TT_LIGHT_REFIT_MAX_NODES)
+        return fail(c, TT_ERR_UNSUPPORTED, "tt_lights_refit: %u light nodes, more than the %u it can address", d.n_lnodes,
+                    (uint32_t)TT_LIGHT_REFIT_MAX_NODES);
+    SceneDev::LightRefit& R = d.lrefit;
+    const bool dev = (flags & TT_TRACE_DEVICE_PTRS) != 0, cons = (flags & TT_LIGHT_REFIT_CONSERVATIVE) != 0;
+    const bool tlas_pass = transforms != nullptr;
+    if (!R.plan_valid) {
+        tt_lplan::build(host_lights(d), c->host.mesh.data(), R.plan);
+        R.plan_valid = true;
+        R.dev_valid = false;
+    }
+    std::string why;
+    const tt_status cs = tt_lplan::check_call(R.plan, c->host.mesh.data(), (uint32_t)c->host.mesh.size(), (uint32_t)d.lmeshes_host.size(),
+                                              d.n_lnodes, mesh_indices, n_mesh_indices, tlas_pass, dev ? nullptr : transforms,
+                                              n_transforms, why);
+    if (cs != TT_OK) return fail(c, cs, "tt_lights_refit: %s", why.c_str());
+    if (dev && tlas_pass && !is_device_ptr(transforms))
+        return fail(c, TT_ERR_INVALID_ARG, "TT_TRACE_DEVICE_PTRS set but transforms are not device memory");
+    TT_HIP(c, hipSetDevice(c->device));
+    const tt_lplan::Plan& P = R.plan;
+    if (!R.dev_valid) {
+        TT_HIP(c, hipStreamSynchronize(c->stream));  // the old plan's arrays may be in use
+        std::vector<int2> up(d.n_lnodes);
+        for (uint32_t i = 0; i < d.n_lnodes; i++) up[i] = make_int2(P.parent[i], P.base[i]);
+        TT_HIP(c, R.up.alloc(up.size()));
+        TT_HIP(c, R.arrive.alloc(up.size()));
+        TT_HIP(c, R.leaf_node.alloc(P.leaf_node.size()));
+        TT_HIP(c, R.leaf_row.alloc(P.leaf_row.size()));
+        TT_HIP(c, hipMemcpy(R.up.p, up.data(), sizeof(int2) * up.size(), hipMemcpyHostToDevice));
+        TT_HIP(c, hipMemset(R.arrive.p, 0, sizeof(uint32_t) * up.size()));
+        TT_HIP(c, hipMemcpy(R.leaf_node.p, P.leaf_node.data(), sizeof(int32_t) * P.leaf_node.size(), hipMemcpyHostToDevice));
+        TT_HIP(c, hipMemcpy(R.leaf_row.p, P.leaf_row.data(), sizeof(int32_t) * P.leaf_row.size(), hipMemcpyHostToDevice));
+        R.dev_valid = true;
+    }
+    // the call's block table: every listed tree's leaves, 256 to a block, no block across two trees
+    std::vector<LightRefitBlock> blocks;
+    for (uint32_t i = 0; i < n_mesh_indices; i++) {
+        const tt_mesh_data& M = c->host.mesh[mesh_indices[i]];
+        const tt_lplan::Tree& T = P.trees.at((uint32_t)M.LightNodeOffset);
+        for (uint32_t k = 0; k < T.leaf_count; k += 256u)
+            blocks.push_back(LightRefitBlock{T.leaf_first + k, std::min(256u, T.leaf_count - k), M.TriOffset, 0u});
+    }
+    const bool stage_x = tlas_pass && !dev;
+    if (R.blocks.n < blocks.size() || (stage_x && R.transforms.n < n_transforms)) {
+        TT_HIP(c, hipStreamSynchronize(c->stream));  // (the old tables may be in use)
+        if (R.blocks.n < blocks.size()) TT_HIP(c, R.blocks.alloc(blocks.size()));
+        if (stage_x && R.transforms.n < n_transforms) TT_HIP(c, R.transforms.alloc(n_transforms));
+    }
+    const LightRefitPlanDev pd{R.up.p, R.arrive.p, R.leaf_node.p, R.leaf_row.p, d.lnodes.p, d.n_lnodes};
+    const tt_light_transform* d_x = transforms;
+    SceneWrite w(c, false);
+    TT_HIP(c, w.err);
+    const size_t b_bytes = sizeof(LightRefitBlock) * blocks.size(), x_bytes = stage_x ? sizeof(tt_light_transform) * n_transforms : 0;
+    if (b_bytes + x_bytes) {
+        void* pin;
+        TT_HIP(c, stage_begin(c, nullptr, b_bytes + x_bytes, pin));
+        if (b_bytes) {
+            std::memcpy(pin, blocks.data(), b_bytes);
+            TT_HIP(c, hipMemcpyAsync(R.blocks.p, pin, b_bytes, hipMemcpyHostToDevice, c->stream));
+        }
+        if (x_bytes) {
+            std::memcpy(static_cast<char*>(pin) + b_bytes, transforms, x_bytes);
+            TT_HIP(c, hipMemcpyAsync(R.transforms.p, static_cast<char*>(pin) + b_bytes, x_bytes, hipMemcpyHostToDevice, c->stream));
+            d_x = R.transforms.p;
+        }
+        TT_HIP(c, stage_end(c));
+    }
+    uint32_t slot;
+    TT_HIP(c, ring_open(c, c->timing, slot));
+    TT_HIP(c, tt_light_refit_forest(pd, R.blocks.p, (uint32_t)blocks.size(), d.ltris.p, d.tris_raw.p, (uint32_t)d.tris_raw.n, cons, c->stream));
+    if (tlas_pass)
+        TT_HIP(c, tt_light_refit_tlas(pd, P.tlas.leaf_first, P.tlas.leaf_count, d_x, n_transforms, cons, c->stream));
+    note_stream_launch(c->stream);
+    TT_HIP(c, ring_close(c, c->timing, slot));
+    TT_HIP(c, w.end());
+    if (!(flags & TT_TRACE_ASYNC)) TT_HIP(c, hipStreamSynchronize(c->stream));
+    return TT_OK;
+}
+
+tt_status tt_scene_read_light_nodes(tt_ctx* c, uint32_t first, uint32_t count, tt_light_node* out) {
+    if (!c) return TT_ERR_INVALID_ARG;
+    if (!c->has_scene || c->scene.n_lnodes == 0) return fail(c, TT_ERR_NO_SCENE, "tt_scene_read_light_nodes: no lights uploaded");
+    if (!out || (uint64_t)first + count > c->scene.n_lnodes)
+        return fail(c, TT_ERR_INVALID_ARG, "tt_scene_read_light_nodes: range out of bounds");
+    TT_HIP(c, hipSetDevice(c->device));
+    SceneRead sr(c);
+    TT_HIP(c, sr.err);
+    TT_HIP(c, hipMemcpyAsync(out, c->scene.lnodes.p + first, sizeof(tt_light_node) * count, hipMemcpyDeviceToHost, c->stream));
+    sr.end();
+    TT_HIP(c, hipStreamSynchronize(c->stream));
+    return TT_OK;
+}
+
+tt_status tt_scene_read_light_tris(tt_ctx* c, uint32_t first, uint32_t count, tt_light_tri* out) {
+    if (!c) return TT_ERR_INVALID_ARG;
+    if (!c->has_scene || c->scene.n_lnodes == 0) return fail(c, TT_ERR_NO_SCENE, "tt_scene_read_light_tris: no lights uploaded");
+    if (!out || (uint64_t)first + count > c->scene.ltris.n)
+        return fail(c, TT_ERR_INVALID_ARG, "tt_scene_read_light_tris: range out of bounds");
+    TT_HIP(c, hipSetDevice(c->device));
+    SceneRead sr(c);
+    TT_HIP(c, sr.err);
+    TT_HIP(c, hipMemcpyAsync(out, c->scene.ltris.p + first, sizeof(tt_light_tri) * count, hipMemcpyDeviceToHost, c->stream));
+    sr.end();
+    TT_HIP(c, hipStreamSynchronize(c->stream));
     return TT_OK;
 }
 

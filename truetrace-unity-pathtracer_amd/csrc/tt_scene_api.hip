@@ -1350,6 +1350,7 @@ tt_status tt_scene_update_meshdata(tt_ctx* c, uint32_t first, uint32_t count, co
                                                       (uint32_t)d.lmeshes_host.size()},
                                     next.data(), (uint32_t)next.size(), h.n_tris, why) != TT_OK)
                 return fail(c, TT_ERR_INVALID_ARG, "light validation failed after meshdata update: %s", why.c_str());
+            c->scene.lrefit.plan_valid = false;  // a tree moved: the next tt_lights_refit rebuilds its plan
         }
     }
     std::memcpy(h.mesh.data() + first, md, sizeof(tt_mesh_data) * count);

@@ -3,7 +3,9 @@
 //    index lists, the recursive build (children allocated in pre-order, so every `left` is even and greater than
 //    its node's index), the 40-byte packing; both constructors;
 //  * the layout of LightNodes / LightTriangles / _LightMeshes (AssetManager.cs:998-1040, :1100-1204, :1681-1707);
-//  * tt_emit_nee_host, the scalar reference of tt_emit_nee: csrc/tt_lights_core.h built by the host compiler.
+//  * tt_emit_nee_host, the scalar reference of tt_emit_nee: csrc/tt_lights_core.h built by the host compiler;
+//  * tt_lights_refit_host, the scalar reference of tt_lights_refit (LightBVHRefitter.compute, level by level as the
+//    reference dispatches it): csrc/tt_light_refit_core.h built by the host compiler; tt_light_refit_math.
 // Where this differs from the reference on purpose (each stated at its place): a stable presort; the merged cone's
 // axis is really rotated (the reference multiplies the rotation by its transpose, which is the identity, and so
 // leaves the axis where it was: the merged cone then need not contain the second cone); asin's argument is
@@ -15,6 +17,8 @@
 #include <vector>
 
 #include "../../include/truetrace_scene.h"
+#include "../csrc/tt_light_refit_core.h"
+#include "../csrc/tt_light_refit_plan_host.h"
 #include "../csrc/tt_lights_check_host.h"
 #include "../csrc/tt_lights_core.h"
 
@@ -437,6 +441,92 @@ tt_status tt_emit_nee_host(const tt_light_node* nodes, uint32_t n_nodes, const t
         }
     }
     *n_shadow = cnt;
+    return TT_OK;
+}
+
+}  // extern "C"
+
+// One tree of the refit plan, the reference's way: its WorkingSet dispatches run from the deepest level up, and
+// the plan's breadth-first order lists the levels top down, so the reverse order evaluates them as dispatched (a
+// level's nodes do not read each other). `leaf` rewrites a leaf node in place.
+template <bool kCons, class Leaf>
+static void refit_tree_host(tt_light_node* nodes, const tt_lplan::Plan& P, const tt_lplan::Tree& T, Leaf&& leaf) {
+    for (uint32_t k = T.bfs_count; k-- > 0;) {
+        const int32_t n = P.bfs[T.bfs_first + k];
+        tt_light_node& nd = nodes[n];
+        if (nd.left < 0) {
+            leaf(nd);
+            continue;
+        }
+        const tt_light_node& a = nodes[T.base + nd.left];
+        nd = tt_lr::union_node<kCons>(a, nodes[T.base + nd.left + 1], nd.left);
+    }
+}
+
+template <bool kCons>
+static void lights_refit_host(tt_light_node* nodes, uint32_t n_nodes, tt_light_tri* ltris, const tt_cuda_triangle* tris,
+                              uint32_t n_tris, const tt_mesh_data* md, const tt_lplan::Plan& P, const uint32_t* mesh_indices,
+                              uint32_t n_mesh_indices, const tt_light_transform* transforms) {
+    for (uint32_t i = 0; i < n_mesh_indices; i++) {
+        const tt_mesh_data& M = md[mesh_indices[i]];
+        const tt_lplan::Tree& T = P.trees.at((uint32_t)M.LightNodeOffset);
+        for (uint32_t k = 0; k < T.leaf_count; k++) {  // TransferKernel
+            tt_light_tri& L = ltris[P.leaf_row[T.leaf_first + k]];
+            const uint64_t agg = (uint64_t)L.TriTarget + (uint64_t)(uint32_t)M.TriOffset;
+            tt_cuda_triangle zero;
+            std::memset(&zero, 0, sizeof zero);
+            tt_lr::transfer_tri(agg < n_tris ? tris[agg] : zero, L);
+        }
+        refit_tree_host<kCons>(nodes, P, T, [&](tt_light_node& nd) { tt_lr::mesh_leaf(ltris[T.start_index + (-(nd.left + 1))], nd); });
+    }
+    if (!transforms) return;
+    tt_light_node zero;
+    std::memset(&zero, 0, sizeof zero);
+    refit_tree_host<kCons>(nodes, P, P.tlas, [&](tt_light_node& nd) {
+        const tt_light_transform& X = transforms[-(nd.left + 1)];
+        // (check_call: SolidOffset is the root of a mesh tree; the zero node stands for D3D's out-of-range read)
+        const tt_light_node root = (uint32_t)X.SolidOffset < n_nodes ? nodes[X.SolidOffset] : zero;
+        tt_lr::tlas_leaf<kCons>(X.Transform, root, nd);
+    });
+}
+
+extern "C" {
+
+tt_status tt_lights_refit_host(tt_light_node* nodes, uint32_t n_nodes, tt_light_tri* ltris, uint32_t n_ltris,
+                               const tt_light_mesh* lmeshes, uint32_t n_lmeshes, const tt_cuda_triangle* tris, uint32_t n_tris,
+                               const tt_mesh_data* meshdata, uint32_t n_mesh, const uint32_t* mesh_indices,
+                               uint32_t n_mesh_indices, const tt_light_transform* transforms, uint32_t n_transforms,
+                               uint32_t flags, char* why, uint32_t why_len) {
+    std::string w;
+    auto done = [&](tt_status st) {
+        if (why && why_len) {
+            std::strncpy(why, w.c_str(), why_len - 1);
+            why[why_len - 1] = 0;
+        }
+        return st;
+    };
+    if (!tris) {
+        w = "null triangles";
+        return done(TT_ERR_INVALID_ARG);
+    }
+    const tt_lcheck::Lights L{nodes, n_nodes, ltris, n_ltris, lmeshes, n_lmeshes};
+    if (tt_lcheck::validate(L, meshdata, n_mesh, n_tris, w) != TT_OK) return done(TT_ERR_INVALID_ARG);
+    tt_lplan::Plan P;
+    tt_lplan::build(L, meshdata, P);
+    const tt_status st = tt_lplan::check_call(P, meshdata, n_mesh, n_lmeshes, n_nodes, mesh_indices, n_mesh_indices,
+                                              transforms != nullptr, transforms, n_transforms, w);
+    if (st != TT_OK) return done(st);
+    if (flags & TT_LIGHT_REFIT_CONSERVATIVE)
+        lights_refit_host<true>(nodes, n_nodes, ltris, tris, n_tris, meshdata, P, mesh_indices, n_mesh_indices, transforms);
+    else
+        lights_refit_host<false>(nodes, n_nodes, ltris, tris, n_tris, meshdata, P, mesh_indices, n_mesh_indices, transforms);
+    return done(TT_OK);
+}
+
+tt_status tt_light_refit_math(uint32_t fn, const float* in, uint32_t n, float* out) {
+    if (fn > 3u || (n && (!in || !out))) return TT_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        out[i] = fn == 0u ? tt_lr::asin_pinned(in[i]) : fn == 1u ? tt_lr::acos_pinned(in[i]) : fn == 2u ? tt_lr::sin_pinned(in[i]) : tt_lr::cos_pinned(in[i]);
     return TT_OK;
 }
 

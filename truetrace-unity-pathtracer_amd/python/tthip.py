@@ -50,6 +50,7 @@ TT_TRACE_FORM_NONE, TT_TRACE_FORM_GENERIC, TT_TRACE_FORM_LEAF = 0, 1, 2
 TT_ROOT_GENERIC, TT_ROOT_ONE_LEAF, TT_ROOT_ONE_INSTANCE = 0, 1, 2
 TT_NEE_NEGATIVE_T = 1 << 9  # tt_emit_nee(_indirect): every written t negated (the PrimaryNEERay / Indirect form)
 TT_LIGHT_MAX_REPS = 322     # SampleLightBVH's loop bound (CommonData.cginc:1132)
+TT_LIGHT_REFIT_CONSERVATIVE = 1 << 10  # tt_lights_refit: every cone contains the cones below it
 TT_SHADOW_RADIANCE_CACHE = 1 << 7    # RadianceCache define (GlobalDefines.cginc:15) for tt_trace_shadow_ex
 TT_SHADOW_VISIBILITY_CHECK = 1 << 8  # VisabilityCheckCompute semantics (CommonData.cginc:710-819)
 TT_TERRAIN_MESH_ID = 9999999   # mesh_id of a terrain hit record (IntersectionKernels.compute:686)
@@ -118,7 +119,10 @@ LIGHT_SAMPLE_DTYPE = np.dtype([("light_tri", "<i4"), ("mesh_index", "<i4"), ("ag
                                ("weight", "<f4"), ("area", "<f4"), ("position", "<f4", 3), ("normal", "<f4", 3)])
 LIGHT_BOUNDS_DTYPE = np.dtype([("BBMax", "<f4", 3), ("BBMin", "<f4", 3), ("w", "<f4", 3), ("phi", "<f4"),
                                ("cosTheta_o", "<f4"), ("cosTheta_e", "<f4"), ("LightCount", "<i4"), ("Pad1", "<f4")])
+# LightBVHTransform (AssetManager.cs:1311-1314): Transform column-major, element (r, c) at [c * 4 + r]
+LIGHT_TRANSFORM_DTYPE = np.dtype([("Transform", "<f4", 16), ("SolidOffset", "<i4")])
 assert (LIGHT_NODE_DTYPE.itemsize, LIGHT_TRI_DTYPE.itemsize, LIGHT_MESH_DTYPE.itemsize, LIGHT_SAMPLE_DTYPE.itemsize) == (40, 40, 28, 48)
+assert LIGHT_TRANSFORM_DTYPE.itemsize == 68
 
 
 class LightParent(C.Structure):
@@ -255,7 +259,8 @@ HIP_SYMBOLS = ["tt_abi_version", "tt_device_count", "tt_ctx_create", "tt_ctx_des
                "tt_object_build_device", "tt_object_read", "tt_object_leaf_order_device", "tt_objects_build_device",
                "tt_scene_update_tlas", "tt_tlas_rebuild", "tt_scene_read_tlas_indices", "tt_group_tlas_rebuild",
                "tt_group_scene_update_tlas", "tt_blas_refit_many", "tt_blas_refit_items_validate", "tt_lights_validate",
-               "tt_scene_upload_lights", "tt_scene_update_light_nodes", "tt_emit_nee", "tt_emit_nee_indirect"]
+               "tt_scene_upload_lights", "tt_scene_update_light_nodes", "tt_emit_nee", "tt_emit_nee_indirect",
+               "tt_lights_refit", "tt_scene_read_light_nodes", "tt_scene_read_light_tris"]
 SCENE_SYMBOLS = ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_blas_free", "tt_scene_assemble",
                  "tt_scene_build_get_info", "tt_scene_build_copy", "tt_scene_build_free", "tt_pack_octahedral",
                  "tt_bvh2_build", "tt_dotnet_sort_by_key", "tt_synth_cornell", "tt_synth_soup", "tt_synth_sponza",
@@ -266,7 +271,7 @@ SCENE_SYMBOLS = ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_blas_f
                  "tt_terrain_trace_detail_host", "tt_terrain_occluded_host", "tt_terrain_normal_host",
                  "tt_scene_assemble_tlas", "tt_scene_build_get_totals", "tt_tlas_build", "tt_light_tris_from_mesh",
                  "tt_light_bvh_build_mesh", "tt_light_bvh_build_tlas", "tt_light_bounds_transform", "tt_lights_assemble",
-                 "tt_emit_nee_host"]
+                 "tt_emit_nee_host", "tt_lights_refit_host", "tt_light_refit_math"]
 
 
 def scene_lib():
@@ -337,8 +342,12 @@ def scene_lib():
                                          C.POINTER(u32), vp, C.POINTER(u32), vp]
         L.tt_emit_nee_host.argtypes = [vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, C.POINTER(TraceParams), vp, i32, i32,
                                        u32, u32, vp, vp, C.POINTER(u32)]
+        L.tt_lights_refit_host.argtypes = [vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, u32,
+                                           C.c_char_p, u32]
+        L.tt_light_refit_math.argtypes = [u32, vp, u32, vp]
         for s in ["tt_light_tris_from_mesh", "tt_light_bvh_build_mesh", "tt_light_bvh_build_tlas",
-                  "tt_light_bounds_transform", "tt_lights_assemble", "tt_emit_nee_host"]:
+                  "tt_light_bounds_transform", "tt_lights_assemble", "tt_emit_nee_host", "tt_lights_refit_host",
+                  "tt_light_refit_math"]:
             getattr(L, s).restype = i32
         for s in ["tt_blas_build", "tt_blas_get_info", "tt_blas_copy", "tt_scene_assemble", "tt_scene_build_get_info",
                   "tt_scene_build_copy", "tt_bvh2_build", "tt_synth_cornell", "tt_synth_soup", "tt_synth_sponza",
@@ -450,6 +459,12 @@ def hip_lib():
             L.tt_emit_nee_indirect.argtypes = [vp, C.POINTER(TraceParams), vp, vp, i32, i32, vp, vp, vp]
             for s in ["tt_lights_validate", "tt_scene_upload_lights", "tt_scene_update_light_nodes", "tt_emit_nee",
                       "tt_emit_nee_indirect"]:
+                getattr(L, s).restype = i32
+        if hasattr(L, "tt_lights_refit"):  # (absent from older libraries)
+            L.tt_lights_refit.argtypes = [vp, vp, u32, vp, u32, u32]
+            L.tt_scene_read_light_nodes.argtypes = [vp, u32, u32, vp]
+            L.tt_scene_read_light_tris.argtypes = [vp, u32, u32, vp]
+            for s in ["tt_lights_refit", "tt_scene_read_light_nodes", "tt_scene_read_light_tris"]:
                 getattr(L, s).restype = i32
         L.tt_bvh2_build_device.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(u32)]
         L.tt_blas_build_device.argtypes = [vp, vp, u32, vp, vp, u32, C.POINTER(u32), vp, C.POINTER(u32)]
@@ -670,6 +685,42 @@ def emit_nee_host(lights: "Lights", scene, rays, n_rays, bounce, far_plane, widt
     if check:
         _check(st, "tt_emit_nee_host")
     return smp[:n_rays], out[:n.value].copy()
+
+
+def light_transforms(local_to_world, solid_offsets) -> np.ndarray:
+    """LIGHT_TRANSFORM_DTYPE rows of tt_lights_refit from row-major (math convention) 4x4 matrices, one per light
+    mesh, and the LightNodeOffset of each light mesh's _MeshData record."""
+    out = np.zeros(len(local_to_world), LIGHT_TRANSFORM_DTYPE)
+    for k, m in enumerate(local_to_world):
+        out["Transform"][k] = unity_colmajor(np.asarray(m))
+    out["SolidOffset"] = np.asarray(solid_offsets, np.int32)
+    return out
+
+
+def lights_refit_host(lights: "Lights", scene, mesh_indices=(), transforms=None, flags=0, check: bool = True):
+    """tt_lights_refit_host: the refitted copy of `lights` (nodes and tris new arrays; the input is not touched).
+    check=False returns (status, reason, lights)."""
+    out = Lights(lights.nodes.copy(), lights.tris.copy(), lights.meshes)
+    mi = np.ascontiguousarray(mesh_indices, np.uint32)
+    x = None if transforms is None else np.ascontiguousarray(transforms, LIGHT_TRANSFORM_DTYPE)
+    why = C.create_string_buffer(512)
+    st = scene_lib().tt_lights_refit_host(_ptr(out.nodes), len(out.nodes), _ptr(out.tris), len(out.tris), _ptr(out.meshes),
+                                          len(out.meshes), _ptr(scene.tris), len(scene.tris), _ptr(scene.meshdata),
+                                          len(scene.meshdata), _ptr(mi) if len(mi) else None, len(mi), _ptr(x),
+                                          0 if x is None else len(x), flags, why, 512)
+    if not check:
+        return st, why.value.decode(), out
+    _check(st, "tt_lights_refit_host: " + why.value.decode())
+    return out
+
+
+def light_refit_math(fn: str, x) -> np.ndarray:
+    """tt_light_refit_math: the refit's pinned "asin" / "acos" / "sin" / "cos" over a float32 array."""
+    xs = np.ascontiguousarray(x, np.float32)
+    out = np.empty_like(xs)
+    _check(scene_lib().tt_light_refit_math(("asin", "acos", "sin", "cos").index(fn), _ptr(xs), xs.size, _ptr(out)),
+           "tt_light_refit_math")
+    return out
 
 
 # ---------------------------------------------------------------- matrices
@@ -1819,6 +1870,35 @@ class Engine:
         if check:
             self._check(st, "tt_scene_update_light_nodes")
         return st
+
+    def refit_lights(self, mesh_indices=(), transforms=None, device=False, asynchronous=False, flags=0,
+                     check: bool = True):
+        """tt_lights_refit. mesh_indices: the _MeshData records whose light trees follow their refit triangles (host);
+        transforms: LIGHT_TRANSFORM_DTYPE rows (host array, or a device buffer of them with device=True), None: no
+        TLAS pass."""
+        mi = np.ascontiguousarray(mesh_indices, np.uint32)
+        if transforms is None:
+            x, nx = None, 0
+        elif isinstance(transforms, np.ndarray):
+            x = np.ascontiguousarray(transforms, LIGHT_TRANSFORM_DTYPE)
+            nx = len(x)
+        else:  # a device tensor of bytes: 68 per row
+            x, nx = transforms, transforms.numel() * transforms.element_size() // 68
+        st = self.L.tt_lights_refit(self.h, _ptr(mi) if len(mi) else None, len(mi), _ptr(x), nx,
+                                    flags | (TT_TRACE_DEVICE_PTRS if device else 0) | (TT_TRACE_ASYNC if asynchronous else 0))
+        if check:
+            self._check(st, "tt_lights_refit")
+        return st
+
+    def read_light_nodes(self, first: int, count: int) -> np.ndarray:
+        out = np.zeros(count, LIGHT_NODE_DTYPE)
+        self._check(self.L.tt_scene_read_light_nodes(self.h, first, count, _ptr(out)), "tt_scene_read_light_nodes")
+        return out
+
+    def read_light_tris(self, first: int, count: int) -> np.ndarray:
+        out = np.zeros(count, LIGHT_TRI_DTYPE)
+        self._check(self.L.tt_scene_read_light_tris(self.h, first, count, _ptr(out)), "tt_scene_read_light_tris")
+        return out
 
     def emit_nee(self, rays, n_rays, bounce, far_plane, width, height, frames=0, max_bounce=3, samples=None,
                  shadow_rays=None, device=False, asynchronous=False, flags=0, check: bool = True):
