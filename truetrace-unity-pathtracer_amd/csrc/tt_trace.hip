@@ -195,6 +195,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     // Data.w (INFO 2), whose place that takes, is only ever tested by write_record: the setup makes the test and a
     // ray that fails it carries PixelIndex 0xffffffff, which writes no texel either. A refilled lane starts after
     // the step: Reps 2, the hit inner children in cg and the hit leaf triangles in tg, or an empty group.
+    // (TT_LEAF_READY_STATE: word 10 is instead octant byte | imask-or-0 << 8 | Reps << 16, see READY below.)
     constexpr bool POOL = LEAF != 0 && TT_LEAF_POOL != 0;
     constexpr bool ROOTSTEP = POOL && TT_LEAF_ROOT_STEP != 0;
     // RESTART (TT_LEAF_RESTART): a lane whose ray finishes while the pool holds prepared rays takes the next one in
@@ -206,6 +207,13 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     // (the form LEAF == 1), so no lane keeps it.
     constexpr bool RESTART = ROOTSTEP && TT_LEAF_RESTART != 0;
     static_assert(!RESTART || LEAF == 1, "the restart parks no world ray: the record write reads it back");
+    // The restart form's bookkeeping knobs (tt_traverse.h): READY, the pool record's words 10 / 11 ready-made
+    // (word 10: octant byte | imask-or-0 << 8 | Reps << 16); MASKB, ballots from the lane mask; POPLAST, the advance
+    // pops after the restart; EMPTYG, the node phase's empty-group branch writes nothing.
+    constexpr bool READY = RESTART && TT_LEAF_READY_STATE != 0;
+    constexpr bool MASKB = RESTART && TT_LEAF_MASK_BALLOT != 0;
+    constexpr bool POPLAST = RESTART && TT_LEAF_POP_LAST != 0;
+    constexpr bool EMPTYG = RESTART && TT_LEAF_EMPTY_GROUP != 0;
     constexpr int tt_lds_depth = lds_depth_of<LEAF>();  // the LDS part of the stack (TT_PUSH / TT_POP)
     static_assert(!POOL || TT_CHUNK_BIG == TT_WAVE, "the prepared-ray pool holds one chunk, one slot per lane");
     __shared__ uint2 s_stack[tt_lds_depth][TT_BLOCK];
@@ -328,14 +336,15 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     };
     // :229-241: the finished ray's hit record and _PrimaryTriangleInfo
     auto finish_ray = [&]() {
-        const bool hit = write_record<INFO, LEAF>(A, ray_index_of(ray_index), pix, col_w, best, world_ray(), mesh_id,
-                                                  TriOffset);
+        const bool hit = write_record<INFO, LEAF>(A, ray_index_of(ray_index), pix, READY ? -1.0f : col_w, best, world_ray(),
+                                                  mesh_id, TriOffset);
         if (STATS) c_hits += hit ? 1u : 0u;
         (void)hit;
         if (ORD) record_chunk_cost(A, swizzle, ray_index, Reps);
     };
     // POOL: a lane's start on work index widx from the pool record of its slot
-    auto start_from = [&](const uint32_t widx, const uint4 p0, const uint4 p1, const uint4 p2) {
+    // (zero_stack false: the caller knows stack_size is 0 -- a lane that finishes has an empty stack)
+    auto start_from = [&](const uint32_t widx, const uint4 p0, const uint4 p1, const uint4 p2, const bool zero_stack) {
         TT_DL(19, true);
         ray_index = RESTART ? widx : ray_of(widx);
         ray.ox = __uint_as_float(p0.x);
@@ -348,7 +357,14 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
         ray.iy = __uint_as_float(p1.w);
         ray.iz = __uint_as_float(p2.x);
         pix = p2.y;
-        if (ROOTSTEP) {
+        if (READY) {
+            // words 10 / 11 as the setup left them for this: one instruction per value (col_w is not kept: the
+            // setup has made write_record's test of Data.w and the record writes pass -1)
+            oct = __builtin_amdgcn_perm(p2.z, p2.z, 0u);  // the octant byte in all four
+            cg = make_uint2(root_cg_x, __builtin_amdgcn_perm(p2.w, p2.z, 0x070c0c01u));  // hit inner children | imask, or 0
+            tg = make_uint2(root_tg_x, p2.w & 0x00ffffffu);
+            Reps = (int32_t)(p2.z >> 16);
+        } else if (ROOTSTEP) {
             col_w = -1.0f;  // (the setup has made write_record's test of Data.w: see there)
             oct = p2.z & 0x7fffffffu;
             // node_group / tri_group of the setup's step. Without a hit inner child the node group is
@@ -380,7 +396,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
         best.mesh_id = 0;
         best.tri_id = -1;
         if (!ROOTSTEP) tg = make_uint2(0u, 0u);
-        stack_size = 0;
+        if (zero_stack) stack_size = 0;
         if (!ROOTSTEP) Reps = 1;
     };
     (void)start_from;
@@ -389,7 +405,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     while (true) {
         TT_DB(0);
         // ---------------------------------------------------------------- refill
-        const uint64_t idle = __ballot((int32_t)tg.y < 0);
+        const uint64_t idle = lane_mask<MASKB>((int32_t)tg.y < 0);
         // (two 32-bit counts: written as __popcll, the compiler keeps the count 64-bit and tests it with two
         // VALU v_cmp_*_u64 per iteration)
         const uint32_t n_idle = (uint32_t)__builtin_popcount((uint32_t)idle) + (uint32_t)__builtin_popcount((uint32_t)(idle >> 32));
@@ -439,7 +455,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
             TT_DB(13);
             WideState st{{ray, world_ray(), cg, tg, oct, stack_size, tlas_ss, NodeOffset, TriOffset, MatOffset, Reps,
                           ray_index_of(ray_index), tid, gtid, (int32_t)tg.y >= 0},
-                         best, mesh_id, pix, col_w};
+                         best, mesh_id, pix, READY ? -1.0f : col_w};
             regroup<2, LEAF>(st, __ballot((int32_t)tg.y >= 0), lane);
             auto finish_wide = [&](const WideState& w) {
                 const bool hit = write_record<INFO, LEAF>(A, w.ray_index, w.pix, w.col_w, w.best, w.wray, mesh_id, TriOffset);
@@ -463,7 +479,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
             // a wave carrying a long ray (>= TT_LONG_PRIO node steps so far) issues ahead of the others until
             // its next refill without one: the long ray's dependent chain, not the wave's share of issue,
             // is what sets a small launch's length (the degenerate-direction rays)
-            if (__ballot((int32_t)tg.y >= 0 && Reps >= TT_LONG_PRIO) != 0ull) __builtin_amdgcn_s_setprio(TT_LONG_PRIO_LEVEL);
+            if (lane_mask<MASKB>((int32_t)tg.y >= 0 && Reps >= TT_LONG_PRIO) != 0ull) __builtin_amdgcn_s_setprio(TT_LONG_PRIO_LEVEL);
             else __builtin_amdgcn_s_setprio(0);
 #endif
             // wave-uniform: take from the wave's pool first, then one dequeue for the rest
@@ -472,6 +488,10 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
             if (avail < n_idle && more) {
                 new_count = sched_reserve(A.ctl, n_rays, n_tiles, lane, n_idle - avail, wave_id, S, new_base);
                 more = new_count > 0 ? 1u : 0u;
+                if constexpr (RESTART && TT_LEAF_UNIFORM_SEG != 0) {  // the segment state too is the wave's, not a lane's
+                    S.seg = __builtin_amdgcn_readfirstlane(S.seg);
+                    S.dead = __builtin_amdgcn_readfirstlane(S.dead);
+                }
                 // a reservation is one whole 64-ray work chunk (TT_CHUNK_BIG, chunk-aligned segments): the
                 // adaptive order maps it to the ray chunk it dequeues (one wave-uniform load)
                 if (ORD && A.order && new_count > 0)
@@ -487,7 +507,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                 const bool take = (int32_t)tg.y < 0 && widx != 0xffffffffu;
                 // slots left from the previous chunk are read before the new chunk overwrites the pool
                 const bool take_left = take && lane_prefix(idle) < min(avail, n_idle);
-                auto start_ray = [&](const uint4 p0, const uint4 p1, const uint4 p2) { start_from(widx, p0, p1, p2); };
+                auto start_ray = [&](const uint4 p0, const uint4 p1, const uint4 p2) { start_from(widx, p0, p1, p2, true); };
                 uint4 p0 = make_uint4(0u, 0u, 0u, 0u), p1 = p0, p2 = p0;
                 if (take_left) {
                     const uint32_t slot = pcol + (widx & 63u);
@@ -536,7 +556,8 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                             // write_record's test of Data.w (INFO 2) is made here: where it fails the record carries
                             // no pixel (a PixelIndex past the frame writes no texel either)
                             if (INFO == 2 && !(cw == -1.0f || (float)A.bounce == cw)) q2.y = 0xffffffffu;
-                            q2.z = o | g.y;
+                            // READY: Reps is 2 after the step, 1 where the ray missed the root's box (o is 0 there)
+                            q2.z = READY ? ((o & 0xffu) | (root_hit ? 0x20000u : 0x10000u)) : (o | g.y);
                             q2.w = 0u;
                             // (the record goes out before the step, which then holds only what it reads; the step
                             // adds its mask)
@@ -546,7 +567,14 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                             // the BLAS root's node step, as the loop would make it first (best.t is FarPlane there)
                             if (root_hit) {
                                 TT_DB(28);
-                                s_pool[2][tid].w = node_intersect(rn.n0, rn.n1, rn.n2, rn.n3, rn.n4, r, o, A.far_plane);
+                                const uint32_t hm = node_intersect(rn.n0, rn.n1, rn.n2, rn.n3, rn.n4, r, o, A.far_plane);
+                                if (READY) {  // the node group of a step that hit no inner child is empty: no imask
+                                    // (the imask of this setup's own read of the root: no lane needs root_imask then)
+                                    const uint32_t im = (hm & 0xff000000u) ? (rn.n0.w >> 24) << 8 : 0u;
+                                    reinterpret_cast<uint2*>(&s_pool[2][tid])[1] = make_uint2((o & 0xffu) | 0x20000u | im, hm);
+                                } else {
+                                    s_pool[2][tid].w = hm;
+                                }
                             }
                         }
                     }
@@ -685,7 +713,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                     TT_REPORT_OVERFLOW(A);
                     keep_record(A, ray_index_of(ray_index));
                 }
-            } else {  // :188-191
+            } else if (!EMPTYG) {  // :188-191 (EMPTYG: only a lane that started with both groups empty comes here)
                 tg = cg;
                 cg = make_uint2(0u, 0u);
             }
@@ -724,15 +752,22 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
             // the pool state stays wave-uniform (SGPRs); the path without a finishing lane is one pop.
             const bool used_up = tg.y == 0u && (cg.y & 0xff000000u) == 0u;
             const bool finishing = used_up && stack_size == 0;
+            // POPLAST: the lanes that pop, decided here and popped after the restart block (the two touch different
+            // lanes and different LDS: the order between them changes nothing)
+            const bool popping = used_up && stack_size != 0;
             if (used_up) {
                 TT_DB(10);
                 TT_DL(31, finishing);
-                if (stack_size != 0) {
+                if (!POPLAST && stack_size != 0) {
                     TT_DB(11);
                     TT_POP(cg);
                 }
             }
-            const uint64_t fin = __ballot(finishing);
+            // (MASKB: compare by compare -- the ballot of an AND of compares still goes through a 0 / 1 value -- and
+            // the masks joined on the scalar side)
+            const uint64_t fin = MASKB ? (lane_mask<MASKB>(tg.y == 0u) & lane_mask<MASKB>((cg.y & 0xff000000u) == 0u) &
+                                          lane_mask<MASKB>(stack_size == 0))
+                                       : lane_mask<false>(finishing);
             if (fin != 0ull) {  // wave-uniform
                 TT_DB(32);
                 const uint32_t n_fin = (uint32_t)__builtin_popcount((uint32_t)fin) + (uint32_t)__builtin_popcount((uint32_t)(fin >> 32));
@@ -746,14 +781,28 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                         const uint32_t slot = (tid - lane) + (widx & 63u);
                         const uint4 p0 = s_pool[0][slot], p1 = s_pool[1][slot], p2 = s_pool[2][slot];
 #ifdef TT_TEST_PARK_SWAP  // (tests only: a wrong parked word must show in the records)
-                        s_pool[0][slot] = make_uint4((uint32_t)best.tri_id, __float_as_uint(best.t), __float_as_uint(best.v),
-                                                     __float_as_uint(best.u));
+                        const float park_u = best.v, park_v = best.u;
 #else
-                        s_pool[0][slot] = make_uint4((uint32_t)best.tri_id, __float_as_uint(best.t), __float_as_uint(best.u),
-                                                     __float_as_uint(best.v));
+                        const float park_u = best.u, park_v = best.v;
 #endif
-                        reinterpret_cast<uint2*>(&s_pool[1][slot])[0] = make_uint2(ray_index, pix);
-                        start_from(widx, p0, p1, p2);
+                        if (READY) {  // word by word: each store takes its value where it lies
+                            // (volatile: left to itself the compiler joins them into a b128 and a b64 again and builds
+                            // their register tuples)
+                            typedef __attribute__((address_space(3))) volatile uint32_t lds_word;
+                            lds_word* k0 = (lds_word*)&s_pool[0][slot];
+                            lds_word* k1 = (lds_word*)&s_pool[1][slot];
+                            k0[0] = (uint32_t)best.tri_id;
+                            k0[1] = __float_as_uint(best.t);
+                            k0[2] = __float_as_uint(park_u);
+                            k0[3] = __float_as_uint(park_v);
+                            k1[0] = ray_index;
+                            k1[1] = pix;
+                        } else {
+                            s_pool[0][slot] = make_uint4((uint32_t)best.tri_id, __float_as_uint(best.t), __float_as_uint(park_u),
+                                                         __float_as_uint(park_v));
+                            reinterpret_cast<uint2*>(&s_pool[1][slot])[0] = make_uint2(ray_index, pix);
+                        }
+                        start_from(widx, p0, p1, p2, !POPLAST);  // (a finishing lane's stack is empty)
                     } else {
                         pending = true;  // no prepared ray left: written at the next refill (or when the wave drains)
                         tg.y = TT_IDLE;
@@ -764,6 +813,10 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                     parked |= m << (pool_next & 63u);
                     pool_next += n_take;
                 }
+            }
+            if (POPLAST && popping) {
+                TT_DB(11);
+                TT_POP(cg);
             }
         } else if (tg.y == 0u && (cg.y & 0xff000000u) == 0u) {
             TT_DB(10);

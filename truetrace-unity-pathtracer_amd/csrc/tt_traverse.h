@@ -74,6 +74,42 @@
 #ifndef TT_LEAF_RESTART_MIN
 #define TT_LEAF_RESTART_MIN 16
 #endif
+// The bookkeeping of the restart form's advance and ray start, one knob per part (1: new, 0: the code before, A/B;
+// profiles/r20/advance/). They change which instructions keep a lane's state, never the state: every ray keeps its
+// arithmetic and its order.
+// TT_LEAF_READY_STATE: the chunk setup stores what a starting lane needs ready-made. Word 10 of the pool record is
+// octant byte | (the root's imask where the step hit an inner child, else 0) << 8 | Reps << 16, word 11 the step's
+// hit mask as before: the lane's oct and cg.y are one v_perm_b32 each, Reps one shift, tg.y one AND, and "no hit
+// inner child: cg.y = 0" is decided by the setup at full width. The parked result goes out in 32-bit stores (no
+// register tuples to form), and no lane keeps Data.w (the setup has made its test: write_record gets -1).
+#ifndef TT_LEAF_READY_STATE
+#define TT_LEAF_READY_STATE 1
+#endif
+// TT_LEAF_MASK_BALLOT: the loop's ballots of a bool take the compare's lane mask (__builtin_amdgcn_ballot_w64)
+// where HIP's int __ballot made a 0 / 1 value of it and compared that again.
+#ifndef TT_LEAF_MASK_BALLOT
+#define TT_LEAF_MASK_BALLOT 1
+#endif
+// TT_LEAF_POP_LAST: the advance restarts the finishing lanes first and pops the others' next group after, with
+// the lanes to pop held as a mask: the pop decrements stack_size in place (before, the finish test after the pop
+// kept the old value alive in a second register, with a copy in and a copy out per iteration), and a restarting
+// lane's stack_size, 0 already, is not written.
+#ifndef TT_LEAF_POP_LAST
+#define TT_LEAF_POP_LAST 1
+#endif
+// TT_LEAF_EMPTY_GROUP: the node phase's "no inner child left: the node group becomes the triangle group" branch is
+// only ever reached, in the restart form, by a lane that started with an empty group -- tg.y == 0 and cg.y == 0
+// already (a pop only brings groups with an inner child, the advance takes every other used-up lane) -- so it
+// has nothing to write and the two zeroes it needed at the top of every node phase go.
+#ifndef TT_LEAF_EMPTY_GROUP
+#define TT_LEAF_EMPTY_GROUP 1
+#endif
+// TT_LEAF_UNIFORM_SEG: the dequeue's segment state (SegState: the segment and the exhausted-segment bits) is made
+// wave-uniform after each reservation, like the pool state (TT_UNIFORM_POOL). As lane values the compiler parked
+// the bits in a register that the triangle pass also uses, with a copy out and a copy in per loop iteration.
+#ifndef TT_LEAF_UNIFORM_SEG
+#define TT_LEAF_UNIFORM_SEG 1
+#endif
 #ifndef TT_WAVES_PER_EU
 #define TT_WAVES_PER_EU 0 // __launch_bounds__ min waves per SIMD (0: compiler default)
 #endif
@@ -604,6 +640,14 @@ __device__ __forceinline__ uint32_t sched_reserve(TraceControl* ctl, uint32_t n_
         S.est = 0;
     }
     return 0u;
+}
+
+// The lanes with p as a 64-bit mask. MASK (TT_LEAF_MASK_BALLOT, the leaf-TLAS restart form): straight from the
+// compare's lane mask, no 0 / 1 value in between.
+template <bool MASK>
+__device__ __forceinline__ uint64_t lane_mask(bool p) {
+    if constexpr (MASK) return __builtin_amdgcn_ballot_w64(p);
+    return __ballot(p);
 }
 
 __device__ __forceinline__ uint32_t lane_prefix(uint64_t mask) {
