@@ -1,6 +1,6 @@
 """The ready-made lane state and the reordered advance of the leaf-TLAS closest-hit kernels (tt_trace_leaf_kernel,
-csrc/tt_trace.hip: TT_LEAF_READY_STATE, TT_LEAF_MASK_BALLOT, TT_LEAF_POP_LAST, TT_LEAF_EMPTY_GROUP,
-TT_LEAF_UNIFORM_SEG). The chunk setup stores in words 10 and 11 of a pool record what a starting lane takes verbatim
+csrc/tt_trace_leaf.h: the pool record's ready-made state word, the ballots from the compares' lane masks, the pop after
+the restart, the empty-group branch that writes nothing, the wave-uniform segment state). The chunk setup stores in words 10 and 11 of a pool record what a starting lane takes verbatim
 (octant byte, imask-or-0, Reps; the root step's hit mask), a finishing lane parks its result word by word, restarts,
 and the other used-up lanes pop afterwards. None of it may change a byte: every case runs in this process (the
 leaf-TLAS kernels), on the oracle, in a child process with TT_LEAF_KERNEL=0 (the generic kernels, which have none of

@@ -1,5 +1,5 @@
-"""The restart of finished lanes in the leaf-TLAS closest-hit kernels (tt_trace_leaf_kernel, csrc/tt_trace.hip,
-TT_LEAF_RESTART): a lane whose ray finishes while the wave's pool holds prepared rays takes the next one in the same
+"""The restart of finished lanes in the leaf-TLAS closest-hit kernels (tt_trace_leaf_kernel,
+csrc/tt_trace_leaf.h): a lane whose ray finishes while the wave's pool holds prepared rays takes the next one in the same
 advance block, parks the finished ray's result in the pool slot it has just consumed, and the wave writes the parked
 records at full width before the next chunk setup, before the cooperative drain and at its exit. Every ray's hit
 record, its _PrimaryTriangleInfo texel and its entry of the compact stream must be written exactly once.

@@ -1,5 +1,5 @@
-"""The BLAS root's node step of the leaf-TLAS closest-hit kernels (tt_trace_leaf_kernel, csrc/tt_trace.hip,
-TT_LEAF_ROOT_STEP): the chunk setup steps the instance's BLAS root for all 64 rays at once, from wave-uniform loads
+"""The BLAS root's node step of the leaf-TLAS closest-hit kernels (tt_trace_leaf_kernel,
+csrc/tt_trace_leaf.h): the chunk setup steps the instance's BLAS root for all 64 rays at once, from wave-uniform loads
 of the node, and the prepared-ray pool carries the step's hit mask, so a refilled lane starts after it -- with inner
 children to visit, with leaf triangles pending, or with an empty group.
 

@@ -2,7 +2,7 @@
 """Per-block execution counts of the closest-hit kernel (TT_DIAG_BLOCKS build: `make variant NAME=diag
 VFLAGS=-DTT_DIAG_BLOCKS`, run with TT_HIP_LIB=lib/variants/libtruetrace_hip_diag.so) on the bench's C2
 workload -- the 1080p jittered primary launch and its compacted bounce-1 launch, one launch each -- or
-C4 (argument c4). Counters (csrc/tt_trace.hip, tt_wide.h; wave executions unless noted):
+C4 (argument c4). Counters (csrc/tt_trace.hip, tt_trace_leaf.h, tt_wide.h; wave executions unless noted):
 
   0 loop iterations        1 record-write batches   2 refill blocks        3 dequeues (atomics)
   4 ray setups             5 node-phase entries     6 node steps           7 pushes
@@ -11,12 +11,12 @@ C4 (argument c4). Counters (csrc/tt_trace.hip, tt_wide.h; wave executions unless
  17 lanes in node steps   18 lanes in triangle passes   19 lanes refilled
  20/21/22 drain node steps (G = 2/4/8)   23 rays in drain node steps
  24/25/26 drain triangle passes (G = 2/4/8)   27 rays in drain triangle passes
- 28 chunk-setup node steps (TT_LEAF_ROOT_STEP: the BLAS root's step of a whole chunk)
+ 28 chunk-setup node steps (the leaf-TLAS loop: the BLAS root's step of a whole chunk)
  29 lanes in chunk-setup node steps (rays that hit the TLAS root's box)
  30 idle lanes (lanes without a ray after the refill block, summed over the loop iterations)
  31 lanes finishing in advance blocks   32 advance blocks in which at least one lane finishes
- 33 lanes restarted in the advance (TT_LEAF_RESTART: the next prepared ray taken from the pool at once)
- 34 full-width writes of parked results (TT_LEAF_RESTART)   35 records they write
+ 33 lanes restarted in the advance (the leaf-TLAS loop: the next prepared ray taken from the pool at once)
+ 34 full-width writes of parked results (the leaf-TLAS loop)   35 records they write
 
 Weighted by each block's static VALU count (tools/isa_blocks.py on the product kernel's ISA; the
 table is --static JSON), this gives VALU per ray by block. Output: JSON on stdout."""

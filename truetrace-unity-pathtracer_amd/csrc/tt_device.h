@@ -171,7 +171,7 @@ __host__ __device__ inline RootLeaf root_leaf_of(const uint32_t* w) {
     R.bits = (meta >> 5) << (meta & 0x1fu);
     return R;
 }
-// The leaf-TLAS kernels (tt_trace.hip, trace_body<LEAF>): stricter than RootLeaf::ok -- the root's one leaf
+// The leaf-TLAS kernels (tt_trace_leaf.h, trace_leaf_body): stricter than RootLeaf::ok -- the root's one leaf
 // holds exactly ONE instance (root_leaf_of also accepts a leaf of 2-3), so every ray of the launch switches
 // to the same BLAS through the same LeafMesh record, A.leaf[base_tri + the index of the one bit].
 __host__ __device__ inline bool root_one_instance(const RootLeaf& R) {

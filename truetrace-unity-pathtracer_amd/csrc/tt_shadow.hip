@@ -317,7 +317,7 @@ __device__ __forceinline__ void shadow_body(const ShadowArgs& A) {
                 new_count = sched_reserve(A.ctl, n_rays, n_tiles, lane, n_idle - avail, wave_id, S, new_base);
                 more = new_count > 0 ? 1u : 0u;
             }
-            const PoolTake pt = pool_take<false>(idle, n_idle, new_base, new_count, pool_next, pool_end, more);
+            const PoolTake pt = pool_take(idle, n_idle, new_base, new_count, pool_next, pool_end, more);
             const uint32_t widx = pt.widx;
             pool_next = pt.pool_next;
             pool_end = pt.pool_end;

@@ -28,9 +28,6 @@
 #ifndef TT_REFILL_MIN
 #define TT_REFILL_MIN 20  // refill idle lanes once at least this many are idle (16 -> 20: profiles/r04/ab)
 #endif
-#ifndef TT_PUSH_FAST
-#define TT_PUSH_FAST 1  // the stack push tests only "an LDS entry is free" on its common path (0: A/B; profiles/r04/ab)
-#endif
 #ifndef TT_DRAIN_PRIO
 #define TT_DRAIN_PRIO 2  // s_setprio level a wave takes once its launch's queue is dry (0: off; with TT_LONG_PRIO +0.8%, profiles/r04/ab/r04h_*)
 #endif
@@ -40,75 +37,14 @@
 #ifndef TT_LONG_PRIO_LEVEL
 #define TT_LONG_PRIO_LEVEL 2  // the s_setprio level of TT_LONG_PRIO (A/B: 3 ranks it above draining waves)
 #endif
-#ifndef TT_UNIFORM_POOL
-#define TT_UNIFORM_POOL 1  // readfirstlane the scheduler's pool state after each refill (0: A/B; +1.2% bench, profiles/r04/ab)
-#endif
 #ifndef TT_LDS_STACK
 #define TT_LDS_STACK 12   // stack entries kept in LDS; deeper entries spill to a global area
 #endif
-// The leaf-TLAS closest-hit kernels (tt_trace.hip, trace_body<LEAF>) set the rays of a dequeued chunk up at full
-// width into a per-wave pool of prepared rays in LDS (TT_LEAF_POOL 1; 0: the per-lane setup at refill, for A/B).
-// The pool takes 3 KiB of the wave's LDS, so those kernels keep TT_LEAF_LDS_STACK stack entries there: pool + stack
-// = the 6 KiB of the other kernels, and as many one-wave blocks stay resident per CU.
-#ifndef TT_LEAF_POOL
-#define TT_LEAF_POOL 1
-#endif
+// The leaf-TLAS closest-hit kernels (tt_trace_leaf.h) keep a per-wave pool of prepared rays in LDS. The pool takes
+// 3 KiB of the wave's LDS, so those kernels keep TT_LEAF_LDS_STACK stack entries there: pool + stack = the 6 KiB of
+// the other kernels, and as many one-wave blocks stay resident per CU.
 #ifndef TT_LEAF_LDS_STACK
 #define TT_LEAF_LDS_STACK 6
-#endif
-// With the pool, the chunk setup also makes every ray's first node step of the loop, the one at the instance's BLAS
-// root with t_max = FarPlane, for all 64 rays at once from wave-uniform loads of the node; the pool record carries
-// the step's hit mask and a refilled lane starts after it (TT_LEAF_ROOT_STEP 1; 0: the step stays in the loop, A/B).
-#ifndef TT_LEAF_ROOT_STEP
-#define TT_LEAF_ROOT_STEP 1
-#endif
-// With the pool and the root step, a lane whose ray finishes takes its next prepared ray from the pool in the same
-// advance block instead of idling until TT_LEAF_REFILL_MIN lanes have finished: the finished ray's result is parked
-// in the pool slot just consumed and its record is written later, at full width, before the pool is overwritten
-// (TT_LEAF_RESTART 1; 0: finished lanes wait for the refill, A/B). The refill block then only runs when the pool is
-// empty, once TT_LEAF_RESTART_MIN lanes are idle (the chunk setup is full-width work however few lanes wait for it,
-// but 1 / 4 / 8 / 12 measured no better than 16 and 20 and more worse: profiles/r15/restart/ab.json).
-#ifndef TT_LEAF_RESTART
-#define TT_LEAF_RESTART 1
-#endif
-#ifndef TT_LEAF_RESTART_MIN
-#define TT_LEAF_RESTART_MIN 16
-#endif
-// The bookkeeping of the restart form's advance and ray start, one knob per part (1: new, 0: the code before, A/B;
-// profiles/r20/advance/). They change which instructions keep a lane's state, never the state: every ray keeps its
-// arithmetic and its order.
-// TT_LEAF_READY_STATE: the chunk setup stores what a starting lane needs ready-made. Word 10 of the pool record is
-// octant byte | (the root's imask where the step hit an inner child, else 0) << 8 | Reps << 16, word 11 the step's
-// hit mask as before: the lane's oct and cg.y are one v_perm_b32 each, Reps one shift, tg.y one AND, and "no hit
-// inner child: cg.y = 0" is decided by the setup at full width. The parked result goes out in 32-bit stores (no
-// register tuples to form), and no lane keeps Data.w (the setup has made its test: write_record gets -1).
-#ifndef TT_LEAF_READY_STATE
-#define TT_LEAF_READY_STATE 1
-#endif
-// TT_LEAF_MASK_BALLOT: the loop's ballots of a bool take the compare's lane mask (__builtin_amdgcn_ballot_w64)
-// where HIP's int __ballot made a 0 / 1 value of it and compared that again.
-#ifndef TT_LEAF_MASK_BALLOT
-#define TT_LEAF_MASK_BALLOT 1
-#endif
-// TT_LEAF_POP_LAST: the advance restarts the finishing lanes first and pops the others' next group after, with
-// the lanes to pop held as a mask: the pop decrements stack_size in place (before, the finish test after the pop
-// kept the old value alive in a second register, with a copy in and a copy out per iteration), and a restarting
-// lane's stack_size, 0 already, is not written.
-#ifndef TT_LEAF_POP_LAST
-#define TT_LEAF_POP_LAST 1
-#endif
-// TT_LEAF_EMPTY_GROUP: the node phase's "no inner child left: the node group becomes the triangle group" branch is
-// only ever reached, in the restart form, by a lane that started with an empty group -- tg.y == 0 and cg.y == 0
-// already (a pop only brings groups with an inner child, the advance takes every other used-up lane) -- so it
-// has nothing to write and the two zeroes it needed at the top of every node phase go.
-#ifndef TT_LEAF_EMPTY_GROUP
-#define TT_LEAF_EMPTY_GROUP 1
-#endif
-// TT_LEAF_UNIFORM_SEG: the dequeue's segment state (SegState: the segment and the exhausted-segment bits) is made
-// wave-uniform after each reservation, like the pool state (TT_UNIFORM_POOL). As lane values the compiler parked
-// the bits in a register that the triangle pass also uses, with a copy out and a copy in per loop iteration.
-#ifndef TT_LEAF_UNIFORM_SEG
-#define TT_LEAF_UNIFORM_SEG 1
 #endif
 #ifndef TT_WAVES_PER_EU
 #define TT_WAVES_PER_EU 0 // __launch_bounds__ min waves per SIMD (0: compiler default)
@@ -642,14 +578,6 @@ __device__ __forceinline__ uint32_t sched_reserve(TraceControl* ctl, uint32_t n_
     return 0u;
 }
 
-// The lanes with p as a 64-bit mask. MASK (TT_LEAF_MASK_BALLOT, the leaf-TLAS restart form): straight from the
-// compare's lane mask, no 0 / 1 value in between.
-template <bool MASK>
-__device__ __forceinline__ uint64_t lane_mask(bool p) {
-    if constexpr (MASK) return __builtin_amdgcn_ballot_w64(p);
-    return __ballot(p);
-}
-
 __device__ __forceinline__ uint32_t lane_prefix(uint64_t mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
@@ -658,12 +586,11 @@ __device__ __forceinline__ uint32_t lane_prefix(uint64_t mask) {
 // [pool_next, pool_end) first, then from the new reservation [new_base, new_base + new_count) (sched_reserve's
 // result; 0 rays: none was made or the queue is exhausted), whose rest becomes the pool. Returns this lane's work
 // index (0xffffffff: none) and the pool state after the refill, by value (written through references, the
-// compiler laid the refill's branches out differently). UNIFORM: readfirstlane that state (TT_UNIFORM_POOL; the
-// closest-hit loop only -- the any-hit loop never had it).
+// compiler laid the refill's branches out differently). The closest-hit loops readfirstlane that state to keep it in
+// SGPRs; the any-hit loop never did.
 struct PoolTake {
     uint32_t widx, pool_next, pool_end, more;
 };
-template <bool UNIFORM>
 __device__ __forceinline__ PoolTake pool_take(uint64_t idle, uint32_t n_idle, uint32_t new_base, uint32_t new_count,
                                               uint32_t pool_next, uint32_t pool_end, uint32_t more) {
     const uint32_t avail = pool_end - pool_next;
@@ -678,11 +605,6 @@ __device__ __forceinline__ PoolTake pool_take(uint64_t idle, uint32_t n_idle, ui
         pool_end = new_base + new_count;
     } else {
         pool_next += take_old;
-    }
-    if (UNIFORM) {  // keep the wave-uniform scheduler state in SGPRs (the loop head's tests become SALU)
-        pool_next = __builtin_amdgcn_readfirstlane(pool_next);
-        pool_end = __builtin_amdgcn_readfirstlane(pool_end);
-        more = __builtin_amdgcn_readfirstlane(more);
     }
     return PoolTake{widx, pool_next, pool_end, more};
 }
@@ -718,12 +640,12 @@ int occupancy_of(Kernel kernel) {
 // declares its own (the leaf-TLAS closest-hit loop and its drain: lds_depth_of<LEAF>()).
 namespace {
 constexpr int tt_lds_depth = TT_LDS_STACK;
-template <int LEAF>
+template <bool LEAF>
 constexpr int lds_depth_of() {
-    return LEAF != 0 && TT_LEAF_POOL != 0 ? TT_LEAF_LDS_STACK : TT_LDS_STACK;
+    return LEAF ? TT_LEAF_LDS_STACK : TT_LDS_STACK;
 }
 }  // namespace
-#if TT_PUSH_FAST  // one compare on the common path (an LDS entry is free); overflow / spill only beyond it
+// The push makes one compare on its common path (an LDS entry is free); overflow / spill only beyond it.
 #define TT_PUSH(val, ok)                                                            \
     do {                                                                            \
         if (tt_lds_depth >= TT_STACK_SIZE || stack_size < tt_lds_depth) {           \
@@ -740,20 +662,6 @@ constexpr int lds_depth_of() {
             stack_size++;                                                           \
         }                                                                           \
     } while (0)
-#else
-#define TT_PUSH(val, ok)                                                            \
-    do {                                                                            \
-        if (stack_size == TT_STACK_SIZE) {                                          \
-            ok = false;                                                             \
-        } else {                                                                    \
-            if (tt_lds_depth >= TT_STACK_SIZE || stack_size < tt_lds_depth)         \
-                s_stack[stack_size][tid] = (val);                                   \
-            else                                                                    \
-                spill[(size_t)(stack_size - tt_lds_depth) * spill_stride + gtid] = (val); \
-            stack_size++;                                                           \
-        }                                                                           \
-    } while (0)
-#endif
 #define TT_POP(dst)                                                                 \
     do {                                                                            \
         --stack_size;                                                               \

@@ -89,15 +89,14 @@ __device__ __forceinline__ GroupSource group_source(uint64_t lead, uint32_t lane
 // Regroups the rays led by the lanes in `lead` into groups of GN consecutive lanes: the fields both drains share
 // move here, the callers move their own from the returned source lane.
 // Must run with every lane of the wave enabled (ds_bpermute reads inactive lanes as zero).
-// LEAF (the leaf-TLAS kernels, tt_trace.hip; 1: the world ray is re-read where needed, 2: it stays resident):
-// tlas_ss, best.mesh_id and, in form 1, wray are not part of a ray's state and the four instance words are
-// wave-uniform, so none of them moves.
-template <int GN, int LEAF = 0>
+// LEAF (the leaf-TLAS kernels, tt_trace_leaf.h): tlas_ss, best.mesh_id and wray are not part of a ray's state (the
+// world ray is re-read where a record needs it) and the four instance words are wave-uniform, so none of them moves.
+template <int GN, bool LEAF = false>
 __device__ __forceinline__ uint32_t regroup_ray(DrainRay& s, uint64_t lead, uint32_t lane) {
     const GroupSource g = group_source(lead, lane, GN);
     const uint32_t src = g.lane;
     shfl_ray(s.ray, src);
-    if (LEAF != 1) shfl_ray(s.wray, src);
+    if (!LEAF) shfl_ray(s.wray, src);
     s.cg.x = shfl_u(s.cg.x, src);
     s.cg.y = shfl_u(s.cg.y, src);
     s.tg.x = shfl_u(s.tg.x, src);
@@ -117,7 +116,7 @@ __device__ __forceinline__ uint32_t regroup_ray(DrainRay& s, uint64_t lead, uint
     s.active = g.has;
     return src;
 }
-template <int GN, int LEAF = 0>
+template <int GN, bool LEAF = false>
 __device__ __forceinline__ void regroup(WideState& s, uint64_t lead, uint32_t lane) {
     const uint32_t src = regroup_ray<GN, LEAF>(s, lead, lane);
     s.best.t = shfl_f(s.best.t, src);
@@ -208,7 +207,7 @@ __device__ __forceinline__ uint32_t node_intersect_part(const uint4 n0, const ui
 // set a stack overflow: the reference writes nothing for it); both are called on the group's first lane only.
 // LEAF: every ray is inside the one instance's BLAS for good (st.NodeOffset / TriOffset / MatOffset hold the
 // instance's wave-uniform values): no TLAS leaf -> BLAS switch and no BLAS exit.
-template <bool STATS, bool MATCHECK, int G, int LEAF, class Finish, class Exhaust>
+template <bool STATS, bool MATCHECK, int G, bool LEAF, class Finish, class Exhaust>
 __device__ void wide_phase(const TraceArgs& A, WideState& st, uint2 (*s_stack)[TT_BLOCK], uint2* __restrict__ spill,
                            uint32_t spill_stride, __amdgpu_buffer_rsrc_t nodes, __amdgpu_buffer_rsrc_t tris,
                            uint32_t lane, Counters C, Finish& finish, Exhaust& exhaust) {
